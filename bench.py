@@ -19,9 +19,16 @@ N > 1 (torchrun, one process per GPU, RCCL): the 1B-synapse graph is split in
 N contiguous shards; every GPU sweeps 150M events of its shard per pass
 (capped by the shard: 125M at N = 8), so per-GPU work is fixed -> "weak".
 
-Extra JSON fields: `roofline` (the gate kernel: algorithmic bytes per launch /
-its HIP-event-timed average duration vs 8 TB/s) and `cpu_baseline` (the
-threaded C oracle on this host, rank 0 at N = 1 only).
+A plain run sets up, settles, warms up, times the K steps and prints the one
+JSON line; its `roofline` (the gate kernel: algorithmic bytes per launch / its
+HIP-event-timed average duration vs 8 TB/s) comes from the timed steps
+themselves.  --full adds what takes runs of its own: the sampled single
+launches (`roofline.sampled_*`, `steady`), `reference_layout` (the drop-in
+path over 16-B records) and `cpu_baseline` (the threaded C oracle on this
+host, rank 0 at N = 1 only).
+
+--dump-outputs DIR writes, right after the timed steps, what a caller of the
+timed path holds after its last step (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -61,7 +68,16 @@ def parse():
                     help="untimed passes from the freshly built graph to the steady state, before "
                          "the warm-up (the start-up transient, DESIGN.md §6)")
     ap.add_argument("--config", default="c3", choices=["c2", "c3", "c5"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what the headline figure does not need: the "
+                         "sampled single launches (roofline.sampled_*, steady), the reference-layout "
+                         "path (reference_layout) and the CPU baseline (cpu_baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the state their last step left (lastFired, a "
+                         "fixed seeded sample of the synapse records, outputs, scalars, stats) as "
+                         "DIR/<name>.npy (float32 / float64, under 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="threads of the CPU baseline (0: every CPU this process may run on)")
     ap.add_argument("--cpu-passes", type=int, default=3)
@@ -75,7 +91,7 @@ def parse():
                          "communicator, world 1) instead of the fused single-GPU pass: its per-pass "
                          "overhead (DESIGN.md §7)")
     ap.add_argument("--no-reference-layout", action="store_true",
-                    help="skip the reference_layout sub-object of the default run")
+                    help="with --full: skip the reference_layout sub-object of the default run")
     ap.add_argument("--raw", action="store_true",
                     help="the reference-layout path: abnn_launch_traversal (brain.metal's 14-buffer ABI) over "
                          "caller-owned 16-B SynapsePacked records and u32 lastF at the config's sweep "
@@ -88,6 +104,71 @@ def parse():
 
 
 PLASTICITY = dict(w_prune=0.105, p_new=0.25, w_init=0.5, compact_every=50)
+
+
+# --dump-outputs: the synapse sample is records [0, 65536) (the dense
+# input->output block, where most updates land) and DUMP_CHUNKS further chunks
+# of DUMP_CHUNK records at offsets drawn once from DUMP_SEED -- 1M records;
+# with the 5M-neuron lastFired as float64 (40 MB) the files stay under 64 MB
+DUMP_SEED = 20240611
+DUMP_CHUNK = 32768
+DUMP_CHUNKS = 30
+DUMP_NEURONS = 5_100_000
+
+
+def dump_chunks(span: int) -> list[tuple[int, int]]:
+    """(first, count) of the sampled record ranges among records [0, span)."""
+    head = min(span, 2 * DUMP_CHUNK)
+    out = [(0, head)] if head else []
+    if span - head <= DUMP_CHUNKS * DUMP_CHUNK:
+        if span > head:
+            out.append((head, span - head))
+        return out
+    rng = np.random.default_rng(DUMP_SEED)
+    starts = np.unique(rng.integers(head, span - DUMP_CHUNK + 1, DUMP_CHUNKS) // DUMP_CHUNK * DUMP_CHUNK)
+    return out + [(int(a), DUMP_CHUNK) for a in starts if a >= head]
+
+
+def dump_neurons(values: np.ndarray) -> np.ndarray:
+    """Every neuron's value as float64, or a fixed seeded sample of DUMP_NEURONS of them."""
+    if values.size > DUMP_NEURONS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(values.size, DUMP_NEURONS, replace=False))
+        values = values[idx]
+    return values.astype(np.float64)
+
+
+def write_outputs(dirpath: str, prefix: str, arrays: dict) -> None:
+    os.makedirs(dirpath, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64_000_000, total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(dirpath, f"{prefix}{name}.npy"), a)
+
+
+def dump_outputs(dirpath: str, brain, mode: int, prefix: str = "") -> None:
+    """What a caller of the timed path holds after its last step: lastFired of
+    every neuron, the sampled synapse records (src and dst too: a structural
+    update moves records), the 64-bit checksum of all local records as four
+    16-bit words, read_outputs(), the scalars with the budget the last pass
+    left, and the counters of the timed passes.  Integers are exact in
+    float64 (timestamps stay far below 2^53)."""
+    span = brain.visited_events() if mode == 0 else brain.n_syn()  # a sweep touches the first E records only
+    syn = np.concatenate([brain.download_synapses(a, n) for a, n in dump_chunks(span)])
+    ck = brain.checksum()
+    sc = brain.scalars()
+    st = brain.stats()
+    write_outputs(dirpath, prefix, {
+        "last_fired": dump_neurons(brain.last_fired()),
+        "synapse_src": syn["src"].astype(np.float64),
+        "synapse_dst": syn["dst"].astype(np.float64),
+        "synapse_w": np.ascontiguousarray(syn["w"], dtype=np.float32),
+        "synapse_checksum": np.array([(ck >> s) & 0xFFFF for s in (48, 32, 16, 0)], dtype=np.float64),
+        "outputs": brain.read_outputs().astype(np.float32),
+        "scalars": np.array([sc["clock"], sc["reward"], sc["rbar"], sc["pass_index"], brain.budget()],
+                            dtype=np.float64),
+        "stats": np.array([st[k] for k in sorted(st)], dtype=np.float64),
+    })
 
 
 def algorithmic_bytes(stats: dict, track_visits: bool, random_mode: bool = False) -> int:
@@ -205,7 +286,8 @@ def cpu_baseline(wl, events: int, mode: int, threads: int, timed_passes: int, ex
                       f"(cgroup quota {hc['cgroup_quota_cpus']} CPUs)"}
 
 
-def raw_run(config: str, events_arg: int, settle: int, warmup: int, steps: int, clock_passes: int = 0) -> dict:
+def raw_run(config: str, events_arg: int, settle: int, warmup: int, steps: int, clock_passes: int = 0,
+            dump_dir: str | None = None) -> dict:
     """One step = one pass of abnn_launch_traversal over caller-owned
     buffers in the reference's layouts (brain.cpp:52-69): the host's two
     writes of encode_traversal / inject_inputs (lastF[inputs] = clock,
@@ -273,6 +355,17 @@ def raw_run(config: str, events_arg: int, settle: int, warmup: int, steps: int, 
     dt = time.perf_counter() - t0
     lib.abnn_debug_raw_stats(ws.data_ptr(), g, None)  # the last pass's
     g1, g2 = int(g[0]), int(g[1])
+    if dump_dir:  # the caller's own buffers after the last timed pass
+        rec = torch.cat([recs[a:a + n] for a, n in dump_chunks(E)]).cpu().numpy()
+        write_outputs(dump_dir, "", {
+            "last_fired": dump_neurons(lastF.cpu().numpy().view(np.uint32)),
+            "synapse_src": rec[:, 0].view(np.uint32).astype(np.float64),
+            "synapse_dst": rec[:, 1].view(np.uint32).astype(np.float64),
+            "synapse_w": np.ascontiguousarray(rec[:, 2]).view(np.float32),
+            "scalars": np.concatenate([scal[:2].cpu().numpy().view(np.uint32).astype(np.float64),
+                                       scal[2:].cpu().numpy().view(np.float32).astype(np.float64)]),
+            "stats": np.array([g1, g2], dtype=np.float64),
+        })
     clk = []
     for _ in range(clock_passes):  # untimed passes, each one's per-wave timeline (tools/raw_clock.py)
         step(1)
@@ -343,7 +436,7 @@ def raw_run(config: str, events_arg: int, settle: int, warmup: int, steps: int, 
 
 def raw_main(args) -> None:
     """--raw: the reference-layout path (raw_run) as the bench line itself."""
-    out = raw_run(args.config, args.events, args.settle, args.warmup, args.steps)
+    out = raw_run(args.config, args.events, args.settle, args.warmup, args.steps, dump_dir=args.dump_outputs)
     print(json.dumps(out), file=_JSON_OUT, flush=True)
 
 
@@ -472,16 +565,30 @@ def main():
     brain.synchronize()
     region_ms = float(ev_a.elapsed_time(ev_b))
     stats = brain.stats()
-    # then, untimed: an event pair around a sample of single launches (every
-    # TIMING_EVERY-th; a pair adds a few us to the launch it brackets) for
-    # the min / median and the steady-state check
-    every = timing_every(args.steps)
-    brain.enable_timing(every)
-    step(args.steps)
-    sync()
-    launch_ms = brain.kernel_times()
-    launches = int(launch_ms.size)
-    brain.enable_timing(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, brain, mode, "" if world == 1 else f"rank{rank}_")
+    sampled = None
+    if args.full:
+        # then, untimed: an event pair around a sample of single launches (every
+        # TIMING_EVERY-th; a pair adds a few us to the launch it brackets) for
+        # the min / median and the steady-state check
+        every = timing_every(args.steps)
+        brain.enable_timing(every)
+        step(args.steps)
+        sync()
+        launch_ms = brain.kernel_times()
+        launches = int(launch_ms.size)
+        brain.enable_timing(0)
+        sampled = {
+            "sampled_launches": launches,
+            "sampled_min_launch_ms": round(float(launch_ms.min()), 4) if launches else None,
+            "sampled_median_launch_ms": round(float(np.median(launch_ms)), 4) if launches else None,
+            "timing_every": every,
+            # a launch cannot take longer than the pass it is part of: if the
+            # sample's median says so (beyond the few us an event pair adds to
+            # the launch it brackets), the timed window still held the transient
+            "steady": bool(launches and float(np.median(launch_ms)) <= 1.08 * dt / args.steps * 1e3),
+        }
     if dist is not None:
         tdev = f"cuda:{device}" if backend == "nccl" else "cpu"
         t = torch.tensor([dt], dtype=torch.float64, device=tdev)
@@ -513,14 +620,7 @@ def main():
             "traffic_other_fetch_bytes": traffic.get("other_fetch_bytes") if traffic else None,
             "kernel": "k_gate", "avg_launch_ms": round(avg_gate_ms, 4), "timed_launches": args.steps,
             "launch_ms_source": "HIP event pair around the timed passes / steps (launch + dispatch gap)",
-            "sampled_launches": launches,
-            "sampled_min_launch_ms": round(float(launch_ms.min()), 4) if launches else None,
-            "sampled_median_launch_ms": round(float(np.median(launch_ms)), 4) if launches else None,
-            "timing_every": every,
-            # a launch cannot take longer than the pass it is part of: if the
-            # sample's median says so (beyond the few us an event pair adds to
-            # the launch it brackets), the timed window still held the transient
-            "steady": bool(launches and float(np.median(launch_ms)) <= 1.08 * dt / args.steps * 1e3),
+            **(sampled or {}),
             "algorithmic_bytes_per_launch": int(bytes_per_launch),
             "bytes_formula": ("3*E (24-bit src stream: 2-B lo + 1-B hi per event; E visited events) -- "
                               "DESIGN.md §5" if mode == 0 else
@@ -539,13 +639,13 @@ def main():
             "pass_ms": round(dt / args.steps * 1e3, 4),
         }
         ref_layout = None
-        if world == 1 and default_run and not args.plasticity and not args.no_reference_layout:
+        if args.full and world == 1 and default_run and not args.plasticity and not args.no_reference_layout:
             brain.close()  # its device memory before the reference-layout buffers (16 GB of records)
             del step, brain
             torch.cuda.empty_cache()
             ref_layout = reference_layout_summary(args.config, args.settle)
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             avail = host_cpus()["available"]
             threads = avail if args.cpu_threads <= 0 else max(1, min(args.cpu_threads, avail))
             # random mode on the CPU is ~100x slower per pass: 6 settle passes

@@ -90,7 +90,7 @@ def main():
             rows = sorted(csv.DictReader(open(trace)), key=lambda r: int(r["Start_Timestamp"]))
             g = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows
                  if KERNEL in r["Kernel_Name"].split("(")[0]]
-            # the fused bench samples `steps` more launches after its timed ones; --raw does not
+            # the fused bench --full samples `steps` more launches after its timed ones; --raw does not
             g = g[-2 * steps:-steps] if KERNEL == "k_gate" else g[-steps:]
             lines.append(f"{KERNEL} mean over the {len(g)} timed launches {statistics.mean(g):.2f} us "
                          f"(bench HIP events, span / passes: {json.loads(bj)['roofline']['avg_launch_ms'] * 1e3:.2f} us)")

@@ -101,6 +101,33 @@ class State(C.Structure):
     ]
 
 
+class EngineConfig(C.Structure):
+    """abnn_engine_config -- abnn::EngineConfig (include/abnn/engine.hpp) plus the trace capacity."""
+
+    _fields_ = [
+        ("input_rate_hz", C.c_float), ("peak_decay", C.c_float), ("rate_alpha", C.c_float),
+        ("max_observed", C.c_float),
+        ("filter_tau", C.c_double), ("dt_sec", C.c_double), ("last_loss", C.c_double),
+        ("use_fir", C.c_uint32), ("fir_size", C.c_uint32), ("win_size", C.c_uint32),
+        ("trace_passes", C.c_uint32),
+        ("teacher_seed", C.c_uint64),
+    ]
+
+
+class EngineState(C.Structure):
+    """abnn_engine_state -- the learning driver's scalars, read back after a synchronise."""
+
+    _fields_ = [
+        ("step", C.c_uint64), ("windows", C.c_uint64), ("win_pos", C.c_uint64),
+        ("teach", C.c_uint32),
+        ("max_observed", C.c_float), ("last_reward", C.c_float),
+        ("last_loss", C.c_double),
+    ]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LAYOUT_MAX_ARRAYS = 4
 
 
@@ -166,6 +193,13 @@ SIGNATURES = [
     ("abnn_set_auto_stimulus", C.c_int, [_VP, _U64, _U64]),
     ("abnn_traverse", C.c_int, [_VP, _U32, _VP]),
     ("abnn_synchronize", C.c_int, [_VP, _VP]),
+    ("abnn_default_engine_config", None, [C.POINTER(EngineConfig)]),
+    ("abnn_engine_create", C.c_int, [_VP, C.POINTER(EngineConfig), C.POINTER(_VP)]),
+    ("abnn_engine_destroy", C.c_int, [_VP]),
+    ("abnn_engine_run", C.c_int, [_VP, _VP, _VP, _U32, _VP]),
+    ("abnn_engine_get_state", C.c_int, [_VP, C.POINTER(EngineState)]),
+    ("abnn_engine_get_rates", C.c_int, [_VP, _VP, _VP, _VP, _U32]),
+    ("abnn_engine_read_trace", C.c_int, [_VP, _U64, _U32, _VP, _VP]),
     ("abnn_exchange_bytes", C.c_uint64, [_VP]),
     ("abnn_set_global_events", C.c_int, [_VP, _U64]),
     ("abnn_shard_gate", C.c_int, [_VP, _VP, _VP]),
@@ -201,7 +235,9 @@ SIGNATURES = [
 ]
 
 # entry points new in ABI 10: an older A/B variant build (ABNN_LIB, timing only) may lack them
-ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_comm_create_local")
+ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_comm_create_local",
+                   "abnn_default_engine_config", "abnn_engine_create", "abnn_engine_destroy", "abnn_engine_run",
+                   "abnn_engine_get_state", "abnn_engine_get_rates", "abnn_engine_read_trace")
 
 _lib = None
 

@@ -3,6 +3,7 @@
 * ``build_hip()``    : hipcc --offload-arch=gfx950 -> abnn_amd/libabnn_hip.so
 * ``build_oracle()`` : gcc -> oracle/liboracle.so (test infrastructure)
 * ``build_cpp_example()`` : g++ -> tests/cpp/brain_cpp_test (C++ Brain API over the C-ABI)
+* ``build_learn_test()``  : g++ -> tests/cpp/learn_test (device-resident learning loop vs the oracle)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -16,9 +17,10 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "abnn_amd")
 CSRC = os.path.join(PKG, "csrc")
-HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip")]
+HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
+               os.path.join(CSRC, "learn.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
-                          os.path.join(ROOT, "include", "abnn", "abnn.h")]
+                          os.path.join(CSRC, "learn.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle.so")
@@ -28,6 +30,10 @@ ENGINE_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "engine_test.cpp")
 ENGINE_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "engine_test")
 ENGINE_HOST_SRC = os.path.join(ROOT, "tests", "cpp", "engine_host_test.cpp")
 ENGINE_HOST_BIN = os.path.join(ROOT, "tests", "cpp", "engine_host_test")
+LEARN_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "learn_test.cpp")
+LEARN_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "learn_test")
+LEARN_BENCH_SRC = os.path.join(ROOT, "tools", "learn_bench.cpp")
+LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
@@ -61,7 +67,7 @@ def _run(cmd: list[str]) -> None:
 
 
 def build_hip(force: bool = False, out: str | None = None, defines: list[str] | None = None) -> str:
-    """The three translation units compiled in parallel (each ~20-60 s), then
+    """The translation units compiled in parallel (each ~20-60 s), then
     linked.  out / defines: an experiment build (tools/build_variant.sh)."""
     target = out or LIB
     if force or out or _stale(target, HIP_DEPS):
@@ -139,11 +145,51 @@ def build_engine_tests(force: bool = False) -> tuple[str | None, str | None]:
     return host, gpu
 
 
+def _build_with_oracle(src: str, out: str, force: bool) -> str | None:
+    """A C++ program over the library and the oracle's C restatement
+    (engine_test's recipe)."""
+    if not os.path.exists(src):
+        return None
+    inc = os.path.join(ROOT, "include")
+    hdrs = [os.path.join(inc, "abnn", h) for h in ("engine.hpp", "brain.hpp", "abnn.h")]
+    osrc = os.path.join(ORACLE_DIR, "c1_oracle.c")
+    deps = [src, os.path.join(ROOT, "tests", "cpp", "oracle_brain.hpp"), osrc, LIB, *hdrs]
+    if force or _stale(out, deps):
+        obj = out + ".oracle.o"
+        _run(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-pthread", "-c", "-o", obj, osrc])
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", out, src, obj, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+        os.remove(obj)
+    return out
+
+
+def build_learn_test(force: bool = False) -> str | None:
+    """Test program of the device-resident learning loop (abnn::DeviceBrainEngine
+    on the GPU brain vs BrainEngine<OracleBrain> on the CPU oracle)."""
+    return _build_with_oracle(LEARN_TEST_SRC, LEARN_TEST_BIN, force)
+
+
+def build_learn_bench(force: bool = False) -> str | None:
+    """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
+    if not os.path.exists(LEARN_BENCH_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [LEARN_BENCH_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("engine.hpp", "brain.hpp", "abnn.h"))]
+    if force or _stale(LEARN_BENCH_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", LEARN_BENCH_BIN, LEARN_BENCH_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../abnn_amd"])
+    return LEARN_BENCH_BIN
+
+
 def build_all(force: bool = False) -> None:
     build_hip(force)
     build_oracle(force)
     build_cpp_example(force)
     build_engine_tests(force)
+    build_learn_test(force)
+    build_learn_bench(force)
 
 
 if __name__ == "__main__":

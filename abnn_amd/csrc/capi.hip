@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "engine.h"
+#include "learn.h"
 
 using namespace abnn;
 
@@ -644,6 +645,22 @@ abnn_status run_commit(abnn_brain* b, const int32_t* gathered, uint32_t world, b
     return ABNN_OK;
 }
 
+// One whole single-GPU pass (abnn_traverse's loop body, abnn_engine_run
+// between its boundary launches): the fused launch where the shape has one,
+// else gate + apply; then the commit.
+abnn_status run_pass(abnn_brain* b, hipStream_t s)
+{
+    // the host reads the clock at encode time, before the pass (brain.cpp:127-128)
+    const bool renorm = renorm_due(b);
+    if (b->use_fused && fused_pass_supported(b->d)) {
+        ST_TRY(run_fused(b, s));
+    } else {
+        ST_TRY(run_gate(b, nullptr, s));
+        ST_TRY(run_apply(b, nullptr, 1, 0, s));
+    }
+    return run_commit(b, nullptr, 1, renorm, s);
+}
+
 // RCCL entry points, resolved once: the librccl already loaded in the process
 // (torch's, when the caller imported it: one RCCL per process), else the
 // system's librccl.so.1.
@@ -1227,17 +1244,7 @@ abnn_status abnn_traverse(abnn_brain* b, uint32_t passes, void* stream)
     if (b->d.visit_mark && passes) b->marks_dirty = true;
     HIP_TRY(hipSetDevice(b->device));
     hipStream_t s = pick(b, stream);
-    for (uint32_t i = 0; i < passes; ++i) {
-        // the host reads the clock at encode time, before the pass (brain.cpp:127-128)
-        const bool renorm = renorm_due(b);
-        if (b->use_fused && fused_pass_supported(b->d)) {
-            ST_TRY(run_fused(b, s));
-        } else {
-            ST_TRY(run_gate(b, nullptr, s));
-            ST_TRY(run_apply(b, nullptr, 1, 0, s));
-        }
-        ST_TRY(run_commit(b, nullptr, 1, renorm, s));
-    }
+    for (uint32_t i = 0; i < passes; ++i) ST_TRY(run_pass(b, s));
     return ABNN_OK;
 }
 
@@ -2070,6 +2077,244 @@ abnn_status abnn_load_flat(abnn_brain* b, const char* path)
         b->marks_dirty = false;
     }
     return retally(b, 0, N);
+}
+
+/* ---- device-resident learning loop (learn.hip) ------------- */
+
+// The driver's state lives on the device (LearnState); the host keeps what it
+// needs to enqueue without reading it back: the two RNG states (counter-based
+// draws: a pass's draws are a function of the state before it), the steps
+// enqueued, and two frame buffers (pinned staging + device) used alternately,
+// each guarded by an event recorded after the last launch of the call that
+// read it -- so a call never waits for the call just before it.
+struct abnn_engine {
+    abnn_brain* b = nullptr;
+    abnn_engine_config cfg{};
+    LearnState st{};
+    float* frames_dev[2] = {};
+    float* frames_host[2] = {};
+    hipEvent_t done[2] = {};
+    bool used[2] = {};
+    uint32_t parity = 0;
+    uint64_t teacher_rng = 0;
+    uint64_t step_host = 0;  // steps enqueued so far
+};
+
+namespace {
+
+constexpr uint64_t kSplitMixGamma = 0x9E3779B97F4A7C15ull;
+
+void engine_free(abnn_engine* e)
+{
+    if (!e) return;
+    (void)hipSetDevice(e->b->device);
+    void* ptrs[] = {e->st.sc, e->st.rate, e->st.filt, e->st.fir, e->st.smooth, e->st.spike_window,
+                    e->st.trace_out, e->st.trace_smooth, e->frames_dev[0], e->frames_dev[1]};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    for (int k = 0; k < 2; ++k) {
+        if (e->frames_host[k]) (void)hipHostFree(e->frames_host[k]);
+        if (e->done[k]) (void)hipEventDestroy(e->done[k]);
+    }
+    delete e;
+}
+
+abnn_status engine_alloc(abnn_engine* e)
+{
+    LearnState& st = e->st;
+    const uint64_t no = st.n_out, tp = st.trace_passes;
+    const uint64_t frame_floats = tp * ((uint64_t)st.n_in + no);
+    ST_TRY(dalloc(&st.sc, 1));
+    ST_TRY(dalloc(&st.rate, no));
+    ST_TRY(dalloc(&st.filt, no));
+    ST_TRY(dalloc(&st.fir, st.use_fir ? (uint64_t)st.fir_size * no : 0));
+    ST_TRY(dalloc(&st.smooth, no));
+    ST_TRY(dalloc(&st.spike_window, no));
+    ST_TRY(dalloc(&st.trace_out, tp * no));
+    ST_TRY(dalloc(&st.trace_smooth, tp * no));
+    for (int k = 0; k < 2; ++k) {
+        ST_TRY(dalloc(&e->frames_dev[k], frame_floats));
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->frames_host[k]), std::max<uint64_t>(frame_floats, 1) * 4,
+                              hipHostMallocDefault));
+        HIP_TRY(hipEventCreateWithFlags(&e->done[k], hipEventDisableTiming));
+    }
+    LearnScalars sc{};
+    sc.last_loss = e->cfg.last_loss;
+    sc.max_observed = e->cfg.max_observed;
+    HIP_TRY(hipMemcpy(st.sc, &sc, sizeof(sc), hipMemcpyHostToDevice));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+void abnn_default_engine_config(abnn_engine_config* c)
+{
+    if (!c) return;
+    std::memset(c, 0, sizeof(*c));
+    c->input_rate_hz = 1000.0f;  // INPUT_RATE_HZ, constants.h:9
+    c->peak_decay = 0.999f;      // PEAK_DECAY, constants.h:10
+    c->rate_alpha = 0.5f;        // ENG:146
+    c->max_observed = 0.5f;      // brain-engine.h:54
+    c->filter_tau = 0.02;        // FILTER_TAU, constants.h:12
+    c->dt_sec = 0.0009;          // dT_SEC, constants.h:14
+    c->last_loss = 0.25;         // brain-engine.h:83
+    c->use_fir = 1u;             // USE_FIR, constants.h:13
+    c->fir_size = 20u;           // rate-filter.h:14
+    c->win_size = 1000u;         // WIN_SIZE_, brain-engine.h:81
+    c->trace_passes = 4096u;
+    c->teacher_seed = 1u;
+}
+
+abnn_status abnn_engine_create(abnn_brain* b, const abnn_engine_config* cfg, abnn_engine** out)
+{
+    REQUIRE(b && cfg && out, "null argument");
+    *out = nullptr;
+    REQUIRE(b->dims.global_events == 0, "abnn_engine_create: a sharded handle has no device-resident loop");
+    REQUIRE(cfg->trace_passes >= 1, "abnn_engine_create: trace_passes must be at least 1");
+    REQUIRE(!cfg->use_fir || cfg->fir_size >= 1, "abnn_engine_create: use_fir needs fir_size >= 1");
+    HIP_TRY(hipSetDevice(b->device));
+    abnn_engine* e = new (std::nothrow) abnn_engine();
+    if (!e) {
+        set_err("host allocation failed");
+        return ABNN_ERR_OOM;
+    }
+    e->b = b;
+    e->cfg = *cfg;
+    e->teacher_rng = cfg->teacher_seed;
+    LearnState& st = e->st;
+    st.last_fired = b->d.last_fired;
+    st.clock = b->d.clock;
+    st.reward = b->d.reward;
+    st.n_in = b->dims.n_input;
+    st.n_out = b->dims.n_output;
+    st.use_fir = cfg->use_fir ? 1u : 0u;
+    st.fir_size = cfg->fir_size;
+    st.win_size = cfg->win_size;
+    st.trace_passes = cfg->trace_passes;
+    // pTick = hz * kTickNS * NSEC_PER_SEC, all in float (brain.cpp:76), as abnn_inject_inputs
+    float p_tick = cfg->input_rate_hz * (float)b->params.tick_ns;
+    p_tick = p_tick * (float)1000000000ull;
+    st.p_tick = p_tick;
+    st.rate_alpha = cfg->rate_alpha;
+    st.peak_decay = cfg->peak_decay;
+    st.filt_a = cfg->dt_sec / (cfg->filter_tau + cfg->dt_sec);  // rate-filter.h:30
+    const abnn_status s = engine_alloc(e);
+    if (s != ABNN_OK) {
+        engine_free(e);
+        return s;
+    }
+    *out = e;
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_destroy(abnn_engine* e)
+{
+    REQUIRE(e, "null argument");
+    (void)hipSetDevice(e->b->device);
+    (void)hipDeviceSynchronize();
+    engine_free(e);
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_run(abnn_engine* e, const float* in_frames, const float* expected_frames,
+                            uint32_t passes, void* stream)
+{
+    REQUIRE(e && in_frames && expected_frames, "null argument");
+    abnn_brain* b = e->b;
+    REQUIRE(passes <= e->cfg.trace_passes, "abnn_engine_run: more passes than trace_passes in one call");
+    REQUIRE(b->dims.global_events == 0, "abnn_engine_run: the handle became a shard");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    ST_TRY(pass_error(b));
+    if (passes == 0) return ABNN_OK;
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t s = pick(b, stream);
+    const LearnState& st = e->st;
+    const uint64_t n_in = st.n_in, n_out = st.n_out;
+
+    // this call's frames: staged in the buffer the call before the last one used
+    const uint32_t k = e->parity;
+    if (e->used[k]) HIP_TRY(hipEventSynchronize(e->done[k]));
+    float* hin = e->frames_host[k];
+    float* hex = hin + passes * n_in;
+    std::memcpy(hin, in_frames, passes * n_in * 4);
+    std::memcpy(hex, expected_frames, passes * n_out * 4);
+    if (passes * (n_in + n_out))
+        HIP_TRY(hipMemcpyAsync(e->frames_dev[k], hin, passes * (n_in + n_out) * 4, hipMemcpyHostToDevice, s));
+    const float* din = e->frames_dev[k];
+    const float* dex = din + passes * n_in;
+
+    for (uint32_t p = 0; p <= passes; ++p) {
+        LearnStep sp{};
+        if (p > 0) sp.post_expected = dex + (uint64_t)(p - 1) * n_out;
+        if (p < passes) {
+            sp.pre_in = din + (uint64_t)p * n_in;
+            sp.pre_expected = dex + (uint64_t)p * n_out;
+            sp.inject_state = b->rng;
+            sp.teacher_state = e->teacher_rng;
+        }
+        HIP_TRY(launch_learn_boundary(st, sp, s));
+        if (p == passes) break;
+        // the draws this pass consumed: the handle's stream stays the all-host driver's
+        b->rng += n_in * kSplitMixGamma;
+        e->teacher_rng += n_out * kSplitMixGamma;
+        state_written(b, b->clock_host);  // the pre half may stamp `now`, as abnn_inject_inputs
+        ST_TRY(run_pass(b, s));
+        e->step_host += 1;
+    }
+    HIP_TRY(hipEventRecord(e->done[k], s));
+    e->used[k] = true;
+    e->parity ^= 1u;
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_get_state(abnn_engine* e, abnn_engine_state* out)
+{
+    REQUIRE(e && out, "null argument");
+    ST_TRY(sync_all(e->b));
+    LearnScalars sc{};
+    HIP_TRY(hipMemcpy(&sc, e->st.sc, sizeof(sc), hipMemcpyDeviceToHost));
+    std::memset(out, 0, sizeof(*out));
+    out->step = sc.step;
+    out->windows = sc.windows;
+    out->win_pos = sc.win_pos;
+    out->teach = sc.teach;
+    out->max_observed = sc.max_observed;
+    out->last_reward = sc.last_reward;
+    out->last_loss = sc.last_loss;
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_get_rates(abnn_engine* e, float* rate, float* smooth, uint32_t* spike_window,
+                                  uint32_t n_output)
+{
+    REQUIRE(e, "null argument");
+    REQUIRE(n_output == e->st.n_out, "abnn_engine_get_rates: size must equal n_output");
+    ST_TRY(sync_all(e->b));
+    const size_t bytes = (size_t)n_output * 4;
+    if (rate && bytes) HIP_TRY(hipMemcpy(rate, e->st.rate, bytes, hipMemcpyDeviceToHost));
+    if (smooth && bytes) HIP_TRY(hipMemcpy(smooth, e->st.smooth, bytes, hipMemcpyDeviceToHost));
+    if (spike_window && bytes) HIP_TRY(hipMemcpy(spike_window, e->st.spike_window, bytes, hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_read_trace(abnn_engine* e, uint64_t first_step, uint32_t n, uint8_t* out, float* smooth)
+{
+    REQUIRE(e, "null argument");
+    const uint64_t have = e->step_host, cap = e->st.trace_passes, no = e->st.n_out;
+    REQUIRE(first_step <= have && n <= have - first_step, "abnn_engine_read_trace: a step that has not run");
+    REQUIRE(have - first_step <= cap, "abnn_engine_read_trace: a step no longer held (trace_passes)");
+    ST_TRY(sync_all(e->b));
+    // the ring: step s is at slot s % trace_passes, so the range is at most two pieces
+    for (uint64_t done = 0; done < n && no;) {
+        const uint64_t slot = (first_step + done) % cap, run = std::min<uint64_t>(n - done, cap - slot);
+        if (out)
+            HIP_TRY(hipMemcpy(out + done * no, e->st.trace_out + slot * no, run * no, hipMemcpyDeviceToHost));
+        if (smooth)
+            HIP_TRY(hipMemcpy(smooth + done * no, e->st.trace_smooth + slot * no, run * no * 4,
+                              hipMemcpyDeviceToHost));
+        done += run;
+    }
+    return ABNN_OK;
 }
 
 }  // extern "C"

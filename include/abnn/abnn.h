@@ -315,6 +315,54 @@ abnn_status abnn_set_auto_stimulus(abnn_brain* b, uint64_t first, uint64_t count
 abnn_status abnn_traverse(abnn_brain* b, uint32_t passes, void* stream);
 abnn_status abnn_synchronize(abnn_brain* b, void* stream);
 
+/* ---- device-resident learning loop -------------------------
+ * BrainEngine::run_one_pass (brain-engine.cpp:108-190, restated in
+ * include/abnn/engine.hpp) with the driver's state on the device: one
+ * abnn_engine_run enqueues `passes` whole learning passes -- input injection,
+ * teacher forcing, the traversal, the output read, the rate filter and the
+ * windowed loss -> reward -- and nothing synchronises until the caller asks
+ * for results.  The results are bit-identical to abnn::BrainEngine<Brain>::
+ * run_one_pass called `passes` times with the same brain, config and frames.
+ * Input draws continue the handle's RNG (abnn_inject_inputs' stream); teacher
+ * draws use the engine's own stream (teacher_seed).  One engine per brain; a
+ * sharded handle is refused.  Destroy the engine before its brain.           */
+typedef struct abnn_engine_config {   /* defaults = abnn::EngineConfig's */
+    float input_rate_hz, peak_decay, rate_alpha, max_observed;
+    double filter_tau, dt_sec, last_loss;
+    uint32_t use_fir, fir_size, win_size;
+    uint32_t trace_passes;            /* capacity of the per-pass record, default 4096 */
+    uint64_t teacher_seed;
+} abnn_engine_config;
+typedef struct abnn_engine_state {    /* host view after a synchronise */
+    uint64_t step, windows, win_pos;
+    uint32_t teach;                   /* the reference's `even` */
+    float max_observed, last_reward;
+    double last_loss;
+} abnn_engine_state;
+typedef struct abnn_engine abnn_engine;
+
+void abnn_default_engine_config(abnn_engine_config* cfg);
+abnn_status abnn_engine_create(abnn_brain* b, const abnn_engine_config* cfg, abnn_engine** out);
+abnn_status abnn_engine_destroy(abnn_engine* e);
+/* in_frames: passes x n_input floats, expected_frames: passes x n_output
+ * floats (HOST memory; frame p = what nextInput() / nextExpected() returned
+ * for pass p; copied before the call returns).  Enqueues only: it does not
+ * wait for the passes of an earlier call.  passes <= trace_passes.           */
+abnn_status abnn_engine_run(abnn_engine* e, const float* in_frames, const float* expected_frames,
+                            uint32_t passes, void* stream);
+/* The three below synchronise first (the device, as every state accessor). */
+abnn_status abnn_engine_get_state(abnn_engine* e, abnn_engine_state* out);
+/* rate = the output-spike EWMA, smooth = the last pass's normalised rates;
+ * any of the three may be NULL.  n_output must equal the brain's.           */
+abnn_status abnn_engine_get_rates(abnn_engine* e, float* rate, float* smooth,
+                                  uint32_t* spike_window, uint32_t n_output);
+/* Per-pass record of steps [first_step, first_step + n): out = n x n_output u8
+ * output spikes, smooth = n x n_output normalised rates (either may be NULL).
+ * Held for the last trace_passes steps; an older (or future) step is
+ * ABNN_ERR_INVALID.                                                          */
+abnn_status abnn_engine_read_trace(abnn_engine* e, uint64_t first_step, uint32_t n,
+                                   uint8_t* out, float* smooth);
+
 /* ---- sharded passes (synapse-shard data parallelism) --------
  * One pass on rank r of W = three calls around ONE exchange:
  *   abnn_shard_gate   -> writes this shard's exchange record to `xchg_dev`

@@ -340,6 +340,10 @@ public:
         return c;
     }
     abnn_brain* handle() const { return h_; }
+    // Before a caller changes the device state through handle() (the
+    // device-resident learning loop, engine.hpp): pending Shared-view writes
+    // are sent first and every host view refreshes on its next contents().
+    void device_state_changes() { touch(); }
 
 private:
     static constexpr uint64_t kPiece = 1u << 20;

@@ -293,4 +293,125 @@ private:
     std::atomic<bool> running_{false};
 };
 
+// The same driver with its state on the device (abnn.h abnn_engine_*,
+// DESIGN.md §9): run_passes(n) pulls n input / expected frames from the
+// stimulus, enqueues n whole learning passes with one call and nothing waits
+// until a getter asks for results.  Bit-identical to BrainEngine<Brain> given
+// the same brain, config and stimulus.  Needs abnn.h's C-ABI, so it is
+// compiled only where brain.hpp was included first (BrainEngine<OracleBrain>
+// alone needs no library).
+#ifdef ABNN_ABNN_H
+class DeviceBrainEngine {
+public:
+    explicit DeviceBrainEngine(Brain& brain, EngineConfig cfg = {}, uint32_t trace_passes = 4096)
+        : brain_(brain), n_in_(brain.n_input()), n_out_(brain.n_output())
+    {
+        abnn_engine_config c;
+        abnn_default_engine_config(&c);
+        c.input_rate_hz = cfg.input_rate_hz;
+        c.peak_decay = cfg.peak_decay;
+        c.rate_alpha = cfg.rate_alpha;
+        c.max_observed = cfg.max_observed;
+        c.filter_tau = cfg.filter_tau;
+        c.dt_sec = cfg.dt_sec;
+        c.last_loss = cfg.last_loss;
+        c.use_fir = cfg.use_fir ? 1u : 0u;
+        c.fir_size = (uint32_t)cfg.fir_size;
+        c.win_size = (uint32_t)cfg.win_size;
+        c.trace_passes = trace_passes;
+        c.teacher_seed = cfg.teacher_seed;
+        check(abnn_engine_create(brain.handle(), &c, &e_), "abnn_engine_create");
+    }
+    ~DeviceBrainEngine() { abnn_engine_destroy(e_); }
+    DeviceBrainEngine(const DeviceBrainEngine&) = delete;
+    DeviceBrainEngine& operator=(const DeviceBrainEngine&) = delete;
+
+    void set_stimulus(std::shared_ptr<StimulusProvider> s) { stim_ = std::move(s); }
+
+    // Enqueue n passes (n <= trace_passes) on `stream`; returns without waiting.
+    void enqueue_passes(uint32_t n, void* stream = nullptr)
+    {
+        if (!stim_ || n == 0) return;
+        in_.resize((std::size_t)n * n_in_);
+        ex_.resize((std::size_t)n * n_out_);
+        for (uint32_t p = 0; p < n; ++p) {
+            const std::vector<float> in = stim_->nextInput();
+            const std::vector<float> expected = stim_->nextExpected();
+            if (in.size() != n_in_ || expected.size() != n_out_) throw std::runtime_error("stimulus frame size");
+            std::copy(in.begin(), in.end(), in_.begin() + (std::size_t)p * n_in_);
+            std::copy(expected.begin(), expected.end(), ex_.begin() + (std::size_t)p * n_out_);
+        }
+        brain_.device_state_changes();
+        check(abnn_engine_run(e_, in_.data(), ex_.data(), n, stream), "abnn_engine_run");
+        enqueued_ += n;
+    }
+
+    // n passes, then their output spikes (waits for them).
+    std::vector<std::vector<bool>> run_passes(uint32_t n, void* stream = nullptr)
+    {
+        const uint64_t first = enqueued_;
+        enqueue_passes(n, stream);
+        std::vector<uint8_t> o;
+        trace(first, (uint32_t)(enqueued_ - first), &o, nullptr);
+        std::vector<std::vector<bool>> out;
+        for (uint64_t p = 0; p < enqueued_ - first; ++p)
+            out.emplace_back(o.begin() + p * n_out_, o.begin() + (p + 1) * n_out_);
+        return out;
+    }
+    std::vector<bool> run_one_pass()
+    {
+        std::vector<std::vector<bool>> o = run_passes(1);
+        return o.empty() ? std::vector<bool>{} : o[0];
+    }
+
+    // The per-pass record of steps [first, first + n) (the last trace_passes steps are held).
+    void trace(uint64_t first, uint32_t n, std::vector<uint8_t>* out, std::vector<float>* smooth) const
+    {
+        if (out) out->resize((std::size_t)n * n_out_);
+        if (smooth) smooth->resize((std::size_t)n * n_out_);
+        check(abnn_engine_read_trace(e_, first, n, out ? out->data() : nullptr, smooth ? smooth->data() : nullptr),
+              "abnn_engine_read_trace");
+    }
+
+    abnn_engine_state state() const
+    {
+        abnn_engine_state s;
+        check(abnn_engine_get_state(e_, &s), "abnn_engine_get_state");
+        return s;
+    }
+    double last_loss() const { return state().last_loss; }
+    float last_reward() const { return state().last_reward; }
+    float max_observed() const { return state().max_observed; }
+    uint64_t step() const { return state().step; }
+    uint64_t windows() const { return state().windows; }
+    std::vector<float> rates() const
+    {
+        std::vector<float> v(n_out_);
+        check(abnn_engine_get_rates(e_, v.data(), nullptr, nullptr, n_out_), "abnn_engine_get_rates");
+        return v;
+    }
+    std::vector<float> smooth_rates() const
+    {
+        std::vector<float> v(n_out_);
+        check(abnn_engine_get_rates(e_, nullptr, v.data(), nullptr, n_out_), "abnn_engine_get_rates");
+        return v;
+    }
+    std::vector<uint32_t> spike_window() const
+    {
+        std::vector<uint32_t> v(n_out_);
+        check(abnn_engine_get_rates(e_, nullptr, nullptr, v.data(), n_out_), "abnn_engine_get_rates");
+        return v;
+    }
+    abnn_engine* handle() const { return e_; }
+
+private:
+    Brain& brain_;
+    uint32_t n_in_, n_out_;
+    abnn_engine* e_ = nullptr;
+    std::shared_ptr<StimulusProvider> stim_;
+    std::vector<float> in_, ex_;
+    uint64_t enqueued_ = 0;
+};
+#endif  // ABNN_ABNN_H
+
 }  // namespace abnn

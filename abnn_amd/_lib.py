@@ -128,6 +128,21 @@ class EngineState(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+CENSUS_MAX_BINS = 4096
+CENSUS_HEADER_WORDS = 8
+
+
+class CensusConfig(C.Structure):
+    """abnn_census_config -- the bins and the src / dst ranges of a synapse census (count 0 = any)."""
+
+    _fields_ = [
+        ("lo", C.c_float), ("hi", C.c_float), ("bins", C.c_uint32),
+        ("src_first", C.c_uint32), ("src_count", C.c_uint32),
+        ("dst_first", C.c_uint32), ("dst_count", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 LAYOUT_MAX_ARRAYS = 4
 
 
@@ -180,6 +195,9 @@ SIGNATURES = [
     ("abnn_download_synapses", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_generate_synapses", C.c_int, [_VP, _U64]),
     ("abnn_checksum_synapses", C.c_int, [_VP, _PU64]),
+    ("abnn_census_words", C.c_uint64, [C.POINTER(CensusConfig)]),
+    ("abnn_census_enqueue", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _VP]),
+    ("abnn_census", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _U64]),
     ("abnn_get_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_set_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_get_last_visited", C.c_int, [_VP, _U64, _VP, _U64]),
@@ -200,6 +218,9 @@ SIGNATURES = [
     ("abnn_engine_get_state", C.c_int, [_VP, C.POINTER(EngineState)]),
     ("abnn_engine_get_rates", C.c_int, [_VP, _VP, _VP, _VP, _U32]),
     ("abnn_engine_read_trace", C.c_int, [_VP, _U64, _U32, _VP, _VP]),
+    ("abnn_engine_set_census", C.c_int, [_VP, C.POINTER(CensusConfig), _U32, _U32]),
+    ("abnn_engine_census_count", C.c_uint64, [_VP]),
+    ("abnn_engine_read_census", C.c_int, [_VP, _U64, _U32, _VP, _VP]),
     ("abnn_exchange_bytes", C.c_uint64, [_VP]),
     ("abnn_set_global_events", C.c_int, [_VP, _U64]),
     ("abnn_shard_gate", C.c_int, [_VP, _VP, _VP]),
@@ -237,7 +258,9 @@ SIGNATURES = [
 # entry points new in ABI 10: an older A/B variant build (ABNN_LIB, timing only) may lack them
 ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_comm_create_local",
                    "abnn_default_engine_config", "abnn_engine_create", "abnn_engine_destroy", "abnn_engine_run",
-                   "abnn_engine_get_state", "abnn_engine_get_rates", "abnn_engine_read_trace")
+                   "abnn_engine_get_state", "abnn_engine_get_rates", "abnn_engine_read_trace",
+                   "abnn_census_words", "abnn_census_enqueue", "abnn_census", "abnn_engine_set_census",
+                   "abnn_engine_census_count", "abnn_engine_read_census")
 
 _lib = None
 

@@ -15,6 +15,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
+from . import census as _census
 from ._lib import Dims, Params, Scalars, State, Stats, call
 
 # SynapsePacked {u32 src, u32 dst, f32 w, f32 pad} (brain.metal:11, brain.h:21)
@@ -157,6 +158,24 @@ class Brain:
         v = C.c_uint64()
         call("abnn_checksum_synapses", self._h, C.byref(v))
         return int(v.value)
+
+    def census(self, bins: int, lo: float, hi: float, src=None, dst=None) -> dict:
+        """Synapse census on the device (abnn_census): counts of
+        this handle's records, tombstones and selected records, and a
+        ``bins``-bin histogram over [lo, hi) of the selected weights.  ``src``
+        / ``dst`` are (first, count) neuron ranges, None = any.  Returns
+        records, tombstones, live, selected, under, over, nan, min, max, counts
+        (np.uint64) and edges (census.decode)."""
+        cfg = _census.config(bins, lo, hi, src, dst)
+        words = int(self._lib.abnn_census_words(C.byref(cfg)))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_census", self._h, C.byref(cfg), _ptr(out), words)  # an invalid config fails here
+        return _census.decode(out, cfg)
+
+    def census_enqueue(self, cfg: _lib.CensusConfig, out_ptr: int, stream=None) -> None:
+        """Enqueue a census into device memory at ``out_ptr`` (abnn_census_words(cfg)
+        u64) on ``stream``; nothing synchronises.  Decode with census.decode."""
+        call("abnn_census_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
 
     # ---- neuron state ---------------------------------------------------------------------------
     def last_fired(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:

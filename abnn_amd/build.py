@@ -4,6 +4,7 @@
 * ``build_oracle()`` : gcc -> oracle/liboracle.so (test infrastructure)
 * ``build_cpp_example()`` : g++ -> tests/cpp/brain_cpp_test (C++ Brain API over the C-ABI)
 * ``build_learn_test()``  : g++ -> tests/cpp/learn_test (device-resident learning loop vs the oracle)
+* ``build_census_test()`` : g++ -> tests/cpp/census_test (the synapse census's C++ mirrors)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -18,9 +19,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "abnn_amd")
 CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
-               os.path.join(CSRC, "learn.hip")]
+               os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
-                          os.path.join(CSRC, "learn.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+                          os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"),
+                          os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 ORACLE_LIB = os.path.join(ORACLE_DIR, "liboracle.so")
@@ -32,6 +34,8 @@ ENGINE_HOST_SRC = os.path.join(ROOT, "tests", "cpp", "engine_host_test.cpp")
 ENGINE_HOST_BIN = os.path.join(ROOT, "tests", "cpp", "engine_host_test")
 LEARN_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "learn_test.cpp")
 LEARN_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "learn_test")
+CENSUS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "census_test.cpp")
+CENSUS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "census_test")
 LEARN_BENCH_SRC = os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -170,6 +174,20 @@ def build_learn_test(force: bool = False) -> str | None:
     return _build_with_oracle(LEARN_TEST_SRC, LEARN_TEST_BIN, force)
 
 
+def build_census_test(force: bool = False) -> str | None:
+    """Test program of the synapse census's C++ mirrors (Brain::census,
+    DeviceBrainEngine::read_census vs a host loop over the downloaded records)."""
+    if not os.path.exists(CENSUS_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [CENSUS_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("engine.hpp", "brain.hpp", "abnn.h"))]
+    if force or _stale(CENSUS_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", CENSUS_TEST_BIN, CENSUS_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return CENSUS_TEST_BIN
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -189,6 +207,7 @@ def build_all(force: bool = False) -> None:
     build_cpp_example(force)
     build_engine_tests(force)
     build_learn_test(force)
+    build_census_test(force)
     build_learn_bench(force)
 
 

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "census.h"
 #include "engine.h"
 #include "learn.h"
 
@@ -97,6 +98,7 @@ struct abnn_brain {
     uint32_t* idx_scratch = nullptr;
     uint64_t idx_cap = 0;
     uint64_t* u64_scratch = nullptr;
+    uint64_t* census_out = nullptr;  // abnn_census's device result (allocated by its first call)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
     uint64_t rot = 0;              // passes run by this handle: the bitmap buffers' rotation (never reset)
@@ -167,7 +169,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
+                    b->u64_scratch,  b->census_out, b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -1079,6 +1081,54 @@ abnn_status abnn_checksum_synapses(abnn_brain* b, uint64_t* out)
     ST_TRY(sync_all(b));
     HIP_TRY(launch_checksum(b->d, b->u64_scratch, b->stream));
     HIP_TRY(hipMemcpyAsync(out, b->u64_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+/* ---- synapse census (census.hip) --------------------------- */
+
+uint64_t abnn_census_words(const abnn_census_config* cfg)
+{
+    return census_config_ok(cfg, nullptr) ? ABNN_CENSUS_HEADER_WORDS + (uint64_t)cfg->bins : 0;
+}
+
+namespace {
+
+// The checks of a census on handle b that need no device; *scale for the launch.
+abnn_status census_check(const abnn_brain* b, const abnn_census_config* cfg, float* scale)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(census_config_ok(cfg, scale),
+            "census: bins must be 1..4096, lo < hi both finite with a finite bins / (hi - lo), reserved 0");
+    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= b->n_nrn, "census: src range ends above N_NRN");
+    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= b->n_nrn, "census: dst range ends above N_NRN");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_census_enqueue(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    float scale = 0.0f;
+    ST_TRY(census_check(b, cfg, &scale));
+    HIP_TRY(hipSetDevice(b->device));
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, *cfg, scale, out_dev, (uint32_t)b->cus, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    float scale = 0.0f;
+    ST_TRY(census_check(b, cfg, &scale));
+    REQUIRE(words == abnn_census_words(cfg), "abnn_census: words must equal abnn_census_words(cfg)");
+    ST_TRY(sync_all(b));
+    if (!b->census_out) ST_TRY(dalloc(&b->census_out, ABNN_CENSUS_HEADER_WORDS + ABNN_CENSUS_MAX_BINS));
+    HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, *cfg, scale, b->census_out, (uint32_t)b->cus, b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->census_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return ABNN_OK;
 }
@@ -2098,6 +2148,16 @@ struct abnn_engine {
     uint32_t parity = 0;
     uint64_t teacher_rng = 0;
     uint64_t step_host = 0;  // steps enqueued so far
+    // the census hook (abnn_engine_set_census): a device ring of census_cap
+    // results of census_words u64 each; snapshot k is at slot k % census_cap
+    // and census_steps[k % census_cap] is the step count it was enqueued at
+    bool census_on = false;
+    abnn_census_config census_cfg{};
+    float census_scale = 0.0f;
+    uint32_t census_every = 0, census_cap = 0;
+    uint64_t census_words = 0, census_taken = 0;
+    uint64_t* census_ring = nullptr;
+    std::vector<uint64_t> census_steps;
 };
 
 namespace {
@@ -2109,7 +2169,7 @@ void engine_free(abnn_engine* e)
     if (!e) return;
     (void)hipSetDevice(e->b->device);
     void* ptrs[] = {e->st.sc, e->st.rate, e->st.filt, e->st.fir, e->st.smooth, e->st.spike_window,
-                    e->st.trace_out, e->st.trace_smooth, e->frames_dev[0], e->frames_dev[1]};
+                    e->st.trace_out, e->st.trace_smooth, e->frames_dev[0], e->frames_dev[1], e->census_ring};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; ++k) {
@@ -2253,6 +2313,14 @@ abnn_status abnn_engine_run(abnn_engine* e, const float* in_frames, const float*
             sp.teacher_state = e->teacher_rng;
         }
         HIP_TRY(launch_learn_boundary(st, sp, s));
+        if (e->census_on && p > 0 && e->step_host % e->census_every == 0) {
+            // the boundary launch above closed step step_host: the weights after its pass
+            const uint64_t slot = e->census_taken % e->census_cap;
+            HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, e->census_cfg, e->census_scale,
+                                  e->census_ring + slot * e->census_words, (uint32_t)b->cus, s));
+            e->census_steps[slot] = e->step_host;
+            e->census_taken += 1;
+        }
         if (p == passes) break;
         // the draws this pass consumed: the handle's stream stays the all-host driver's
         b->rng += n_in * kSplitMixGamma;
@@ -2312,6 +2380,55 @@ abnn_status abnn_engine_read_trace(abnn_engine* e, uint64_t first_step, uint32_t
         if (smooth)
             HIP_TRY(hipMemcpy(smooth + done * no, e->st.trace_smooth + slot * no, run * no * 4,
                               hipMemcpyDeviceToHost));
+        done += run;
+    }
+    return ABNN_OK;
+}
+
+abnn_status abnn_engine_set_census(abnn_engine* e, const abnn_census_config* cfg, uint32_t every, uint32_t capacity)
+{
+    REQUIRE(e, "null argument");
+    float scale = 0.0f;
+    if (cfg) {
+        ST_TRY(census_check(e->b, cfg, &scale));
+        REQUIRE(every >= 1 && capacity >= 1, "abnn_engine_set_census: every and capacity must be at least 1");
+    }
+    ST_TRY(sync_all(e->b));  // censuses already enqueued write the ring
+    if (e->census_ring) (void)hipFree(e->census_ring);
+    e->census_ring = nullptr;
+    e->census_on = false;
+    e->census_taken = 0;
+    e->census_steps.clear();
+    if (!cfg) return ABNN_OK;
+    const uint64_t words = abnn_census_words(cfg);
+    ST_TRY(dalloc(&e->census_ring, words * capacity));
+    e->census_steps.assign(capacity, 0);
+    e->census_cfg = *cfg;
+    e->census_scale = scale;
+    e->census_every = every;
+    e->census_cap = capacity;
+    e->census_words = words;
+    e->census_on = true;
+    return ABNN_OK;
+}
+
+uint64_t abnn_engine_census_count(const abnn_engine* e) { return e ? e->census_taken : 0; }
+
+abnn_status abnn_engine_read_census(abnn_engine* e, uint64_t first, uint32_t n, uint64_t* out, uint64_t* steps)
+{
+    REQUIRE(e, "null argument");
+    REQUIRE(e->census_on, "abnn_engine_read_census: no census is set");
+    const uint64_t have = e->census_taken, cap = e->census_cap, words = e->census_words;
+    REQUIRE(first <= have && n <= have - first, "abnn_engine_read_census: a snapshot that has not been taken");
+    REQUIRE(n == 0 || have - first <= cap, "abnn_engine_read_census: a snapshot no longer held (capacity)");
+    ST_TRY(sync_all(e->b));
+    // the ring: snapshot k is at slot k % capacity, so the range is at most two pieces
+    for (uint64_t done = 0; done < n;) {
+        const uint64_t slot = (first + done) % cap, run = std::min<uint64_t>(n - done, cap - slot);
+        if (out)
+            HIP_TRY(hipMemcpy(out + done * words, e->census_ring + slot * words, run * words * sizeof(uint64_t),
+                              hipMemcpyDeviceToHost));
+        if (steps) std::copy_n(e->census_steps.begin() + slot, run, steps + done);
         done += run;
     }
     return ABNN_OK;

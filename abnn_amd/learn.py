@@ -15,6 +15,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
+from . import census as _census
 from ._lib import EngineConfig, EngineState, call
 from .brain import Brain, _stream_ptr
 
@@ -89,6 +90,33 @@ class LearnEngine:
         call("abnn_engine_get_rates", self._h, rate.ctypes.data, smooth.ctypes.data, window.ctypes.data,
              self._n_out)
         return {"rate": rate, "smooth": smooth, "spike_window": window}
+
+    def set_census(self, bins: Optional[int] = None, lo: float = 0.0, hi: float = 1.0, src=None, dst=None, *,
+                   every: int = 1, capacity: int = 1) -> None:
+        """A synapse census (Brain.census's arguments) after every ``every``-th
+        step inside the loop, kept in a device ring of ``capacity`` results;
+        ``set_census(None)`` turns it off.  Restarts the ring."""
+        if bins is None:
+            call("abnn_engine_set_census", self._h, None, 0, 0)
+            self._census_cfg = None
+            return
+        cfg = _census.config(bins, lo, hi, src, dst)
+        call("abnn_engine_set_census", self._h, C.byref(cfg), int(every), int(capacity))
+        self._census_cfg = cfg
+
+    def census_count(self) -> int:
+        """Censuses taken since set_census (host count, no synchronisation)."""
+        return int(_lib.load().abnn_engine_census_count(self._h))
+
+    def census_trace(self, first: int, n: int) -> tuple[np.ndarray, list]:
+        """Snapshots [first, first + n) since set_census: the step counts they
+        were taken at (np.uint64) and the results as dicts (Brain.census's)."""
+        cfg = getattr(self, "_census_cfg", None)
+        words = _census.n_words(cfg) if cfg is not None else 1
+        out = np.zeros((n, words), np.uint64)
+        steps = np.zeros(n, np.uint64)
+        call("abnn_engine_read_census", self._h, int(first), int(n), out.ctypes.data, steps.ctypes.data)
+        return steps, [_census.decode(row, cfg) for row in out]
 
     def trace(self, first_step: int, n: int) -> tuple[np.ndarray, np.ndarray]:
         """Output spikes (n x n_output uint8) and normalised rates (float32) of

@@ -333,6 +333,30 @@ class ShardedBrain:
         self.global_events = int(t.item())
         self.brain.set_global_events(self.global_events)
 
+    def census(self, bins: int, lo: float, hi: float, src=None, dst=None) -> dict:
+        """Brain.census over every shard's records (collective: every rank
+        calls it at the same point and gets the whole graph's result): the
+        local census, then counts and bins summed (all_reduce_sum) and min /
+        max combined on their order keys (all_reduce_max; the minimum as the
+        maximum of the inverted key)."""
+        from . import census as _census
+
+        torch = self._torch
+        cfg = _census.config(bins, lo, hi, src, dst)
+        local = _census.to_words(self.brain.census(bins, lo, hi, src, dst))
+        h = _census.CENSUS_HEADER_WORDS
+        counts = np.concatenate([local[:6], local[h:]]).astype(np.int64)
+        kmin, kmax = (int(_census.order_key(int(local[i]))) for i in (6, 7))
+        t_counts = torch.from_numpy(counts).to(self.xchg.device)
+        t_keys = torch.tensor([0xFFFFFFFF - kmin, kmax], dtype=torch.int64, device=self.xchg.device)
+        self.comm.all_reduce_sum(t_counts)
+        self.comm.all_reduce_max(t_keys)
+        counts = t_counts.cpu().numpy().astype(np.uint64)
+        keys = np.array([0xFFFFFFFF - int(t_keys[0].item()), int(t_keys[1].item())], dtype=np.uint32)
+        bits = np.where(keys >> np.uint32(31), keys ^ np.uint32(0x80000000), ~keys)  # the key's inverse
+        words = np.concatenate([counts[:6], bits.astype(np.uint64), counts[6:]])
+        return _census.decode(words, cfg)
+
     def local_events(self) -> int:
         return self.brain.visited_events()
 

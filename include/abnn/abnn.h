@@ -276,6 +276,47 @@ abnn_status abnn_generate_synapses(abnn_brain* b, uint64_t seed);
 /* Order-sensitive 64-bit checksum of the local synapse array (device-side). */
 abnn_status abnn_checksum_synapses(abnn_brain* b, uint64_t* out);
 
+/* ---- synapse census ----------------------------------------
+ * One streaming pass over the handle's local records [0, n_syn): live and
+ * tombstone counts and a histogram of the selected weights, without moving the
+ * records to the host.  Records past n_syn (the capacity's headroom, the
+ * padding) are never read.
+ * A tombstone is a record with dst == 0xFFFFFFFF.  A record is SELECTED when
+ * it is live and passes both ranges.  A selected record with weight w counts,
+ * in this order: w != w -> NaN; w < lo -> under; w >= hi -> over; otherwise
+ * bin min((uint32_t)((w - lo) * scale), bins - 1), scale = (float)bins /
+ * (hi - lo), every operation a single IEEE fp32 operation.  hi - lo and scale
+ * must be finite.  Min and max are taken over the selected non-NaN weights in
+ * the total order of the sign-flip integer key (-0.0 < +0.0); with none, min
+ * is +inf and max is -inf.  selected == under + over + nan + sum of the bins.
+ * Every word is an integer, so the result is the same for any grid and order
+ * (abnn_amd/census.py restates it in numpy).
+ * Result: ABNN_CENSUS_HEADER_WORDS + bins u64 words:
+ *   0 records scanned (= n_syn)   1 tombstones among them   2 selected
+ *   3 under   4 over   5 NaN
+ *   6 / 7 f32 bits of the minimum / maximum, in the low 32 bits
+ *   8... the bins                                                            */
+#define ABNN_CENSUS_MAX_BINS 4096
+#define ABNN_CENSUS_HEADER_WORDS 8
+typedef struct abnn_census_config {
+    float lo, hi;            /* bins cover [lo, hi); finite, lo < hi                   */
+    uint32_t bins;           /* 1 .. ABNN_CENSUS_MAX_BINS                              */
+    uint32_t src_first, src_count;   /* count 0 = any src; else src in [first, first+count) */
+    uint32_t dst_first, dst_count;   /* likewise for dst                                */
+    uint32_t reserved;       /* 0 */
+} abnn_census_config;         /* 32 bytes */
+/* ABNN_CENSUS_HEADER_WORDS + bins, or 0 for an invalid config (whatever can be
+ * checked without a handle: a range's end is checked against N_NRN below).  */
+uint64_t abnn_census_words(const abnn_census_config* cfg);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, abnn_census_words(cfg)
+ * u64) in stream order on `stream`; no synchronise, so it can sit between
+ * passes.  A shard handle censuses its own records.  ABNN_ERR_INVALID: a null
+ * argument, an invalid config, a range that ends above N_NRN, a handle whose
+ * records are invalid (a failed structural update).  n_syn == 0 is valid.    */
+abnn_status abnn_census_enqueue(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_census_words(cfg)). */
+abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_host, uint64_t words);
+
 /* ---- neuron timestamps / scalars ----------------------------------------- */
 abnn_status abnn_get_last_fired(abnn_brain* b, uint64_t first, uint64_t* out, uint64_t n);
 abnn_status abnn_set_last_fired(abnn_brain* b, uint64_t first, const uint64_t* src, uint64_t n);
@@ -362,6 +403,21 @@ abnn_status abnn_engine_get_rates(abnn_engine* e, float* rate, float* smooth,
  * ABNN_ERR_INVALID.                                                          */
 abnn_status abnn_engine_read_trace(abnn_engine* e, uint64_t first_step, uint32_t n,
                                    uint8_t* out, float* smooth);
+/* A synapse census (above) every `every` steps inside the loop.  cfg NULL =
+ * off.  From now on a census is enqueued right after the boundary launch that
+ * closes every step whose step count is a multiple of `every` (>= 1), into a
+ * device ring of `capacity` (>= 1) results; restarts the ring (and waits for
+ * the device).  The census sees the weights after that step's pass.
+ * abnn_engine_run stays enqueue-only; with the census off it enqueues exactly
+ * what it enqueues without this call.                                        */
+abnn_status abnn_engine_set_census(abnn_engine* e, const abnn_census_config* cfg, uint32_t every, uint32_t capacity);
+/* Censuses taken since abnn_engine_set_census (host-side count, no synchronisation). */
+uint64_t abnn_engine_census_count(const abnn_engine* e);
+/* Snapshots [first, first + n) since abnn_engine_set_census: out = n x
+ * abnn_census_words(cfg) u64, steps = n u64 (the step count each was taken
+ * at); either may be NULL.  Synchronises.  An evicted or not yet taken
+ * snapshot is ABNN_ERR_INVALID.                                              */
+abnn_status abnn_engine_read_census(abnn_engine* e, uint64_t first, uint32_t n, uint64_t* out, uint64_t* steps);
 
 /* ---- sharded passes (synapse-shard data parallelism) --------
  * One pass on rank r of W = three calls around ONE exchange:

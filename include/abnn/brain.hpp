@@ -52,6 +52,24 @@ inline void check(abnn_status s, const char* what)
     throw std::runtime_error(m);
 }
 
+// A census result (abnn.h abnn_census: ABNN_CENSUS_HEADER_WORDS + bins words).
+struct Census {
+    uint64_t records = 0, tombstones = 0, selected = 0, under = 0, over = 0, nan = 0;
+    float min = 0.0f, max = 0.0f;  // +inf / -inf when no selected weight is a number
+    std::vector<uint64_t> counts;  // the bins
+    uint64_t live() const { return records - tombstones; }
+    static Census from_words(const uint64_t* w, uint32_t bins)
+    {
+        Census c;
+        c.records = w[0], c.tombstones = w[1], c.selected = w[2], c.under = w[3], c.over = w[4], c.nan = w[5];
+        const uint32_t lo = (uint32_t)w[6], hi = (uint32_t)w[7];
+        std::memcpy(&c.min, &lo, 4);
+        std::memcpy(&c.max, &hi, 4);
+        c.counts.assign(w + ABNN_CENSUS_HEADER_WORDS, w + ABNN_CENSUS_HEADER_WORDS + bins);
+        return c;
+    }
+};
+
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
@@ -338,6 +356,13 @@ public:
         uint64_t c = 0;
         check(abnn_checksum_synapses(h_, &c), "abnn_checksum_synapses");
         return c;
+    }
+    // Synapse census on the device (abnn_census; the definition is in abnn.h).
+    Census census(const abnn_census_config& cfg) const
+    {
+        std::vector<uint64_t> w(abnn_census_words(&cfg) ? abnn_census_words(&cfg) : 1);
+        check(abnn_census(h_, &cfg, w.data(), abnn_census_words(&cfg)), "abnn_census");
+        return Census::from_words(w.data(), cfg.bins);
     }
     abnn_brain* handle() const { return h_; }
     // Before a caller changes the device state through handle() (the

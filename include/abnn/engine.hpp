@@ -402,11 +402,32 @@ public:
         check(abnn_engine_get_rates(e_, nullptr, nullptr, v.data(), n_out_), "abnn_engine_get_rates");
         return v;
     }
+    // A synapse census after every `every`-th step inside the loop, kept in a
+    // device ring of `capacity` results (abnn_engine_set_census); nullptr = off.
+    void set_census(const abnn_census_config* cfg, uint32_t every = 1, uint32_t capacity = 1)
+    {
+        check(abnn_engine_set_census(e_, cfg, every, capacity), "abnn_engine_set_census");
+        census_bins_ = cfg ? cfg->bins : 0;
+    }
+    uint64_t census_count() const { return abnn_engine_census_count(e_); }
+    // Snapshots [first, first + n) since set_census and the step counts they were taken at.
+    std::vector<Census> read_census(uint64_t first, uint32_t n, std::vector<uint64_t>* steps = nullptr) const
+    {
+        const uint64_t words = ABNN_CENSUS_HEADER_WORDS + (uint64_t)census_bins_;
+        std::vector<uint64_t> w((std::size_t)n * words + 1);
+        if (steps) steps->resize(n);
+        check(abnn_engine_read_census(e_, first, n, w.data(), steps ? steps->data() : nullptr),
+              "abnn_engine_read_census");
+        std::vector<Census> out;
+        for (uint32_t k = 0; k < n; ++k) out.push_back(Census::from_words(w.data() + k * words, census_bins_));
+        return out;
+    }
     abnn_engine* handle() const { return e_; }
 
 private:
     Brain& brain_;
     uint32_t n_in_, n_out_;
+    uint32_t census_bins_ = 0;
     abnn_engine* e_ = nullptr;
     std::shared_ptr<StimulusProvider> stim_;
     std::vector<float> in_, ex_;

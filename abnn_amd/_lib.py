@@ -143,6 +143,35 @@ class CensusConfig(C.Structure):
     ]
 
 
+class SpikesConfig(C.Structure):
+    """abnn_spikes_config -- the spike recorder's capacities, neuron range (count 0 = every neuron) and counts switch."""
+
+    _fields_ = [
+        ("raster_capacity", C.c_uint64), ("pass_capacity", C.c_uint32),
+        ("first", C.c_uint32), ("count", C.c_uint32), ("counts", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class SpikePass(C.Structure):
+    """abnn_spike_pass -- one recorded pass (spikes.SPIKE_PASS_DTYPE is its numpy view)."""
+
+    _fields_ = [
+        ("pass_index", C.c_uint64), ("now", C.c_uint64), ("offset", C.c_uint64),
+        ("count", C.c_uint32), ("epoch", C.c_uint32),
+    ]
+
+
+class SpikesInfo(C.Structure):
+    """abnn_spikes_info -- the recorder's seven u64 words."""
+
+    _fields_ = [(k, C.c_uint64) for k in ("passes_seen", "spikes_seen", "selected_seen", "passes_recorded",
+                                          "spikes_recorded", "passes_dropped", "spikes_dropped")]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 LAYOUT_MAX_ARRAYS = 4
 
 
@@ -198,6 +227,13 @@ SIGNATURES = [
     ("abnn_census_words", C.c_uint64, [C.POINTER(CensusConfig)]),
     ("abnn_census_enqueue", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _VP]),
     ("abnn_census", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _U64]),
+    ("abnn_spikes_start", C.c_int, [_VP, C.POINTER(SpikesConfig)]),
+    ("abnn_spikes_stop", C.c_int, [_VP]),
+    ("abnn_spikes_clear", C.c_int, [_VP, C.c_int]),
+    ("abnn_spikes_get_info", C.c_int, [_VP, C.POINTER(SpikesInfo)]),
+    ("abnn_spikes_read_passes", C.c_int, [_VP, _U64, _U64, _VP]),
+    ("abnn_spikes_read_raster", C.c_int, [_VP, _U64, _U64, _VP]),
+    ("abnn_spikes_read_counts", C.c_int, [_VP, _U64, _U64, _VP]),
     ("abnn_get_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_set_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_get_last_visited", C.c_int, [_VP, _U64, _VP, _U64]),
@@ -260,7 +296,9 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_default_engine_config", "abnn_engine_create", "abnn_engine_destroy", "abnn_engine_run",
                    "abnn_engine_get_state", "abnn_engine_get_rates", "abnn_engine_read_trace",
                    "abnn_census_words", "abnn_census_enqueue", "abnn_census", "abnn_engine_set_census",
-                   "abnn_engine_census_count", "abnn_engine_read_census")
+                   "abnn_engine_census_count", "abnn_engine_read_census",
+                   "abnn_spikes_start", "abnn_spikes_stop", "abnn_spikes_clear", "abnn_spikes_get_info",
+                   "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts")
 
 _lib = None
 

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import census as _census
+from . import spikes as _spikes
 from ._lib import Dims, Params, Scalars, State, Stats, call
 
 # SynapsePacked {u32 src, u32 dst, f32 w, f32 pad} (brain.metal:11, brain.h:21)
@@ -176,6 +177,51 @@ class Brain:
         """Enqueue a census into device memory at ``out_ptr`` (abnn_census_words(cfg)
         u64) on ``stream``; nothing synchronises.  Decode with census.decode."""
         call("abnn_census_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
+
+    # ---- spike recorder (abnn_spikes_*, DESIGN.md §9) -------------------------------------------
+    def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
+        """Start (or restart) the spike recorder: from now on every pass this
+        handle completes appends its spike list -- the dst of every spike, in
+        budget order -- to device buffers of ``raster`` spikes (0: no raster)
+        and ``passes`` pass entries, with no synchronise.  ``neurons`` =
+        (first, count) keeps only those dst; ``counts`` keeps per-neuron counts."""
+        cfg = _spikes.config(raster, passes, neurons, counts)
+        self._spk = None  # a failed start leaves no recorder
+        call("abnn_spikes_start", self._h, C.byref(cfg))
+        self._spk = cfg
+
+    def spikes(self) -> dict:
+        """What the recorder holds (synchronises): ``info`` (abnn_spikes_info
+        as a dict), ``passes`` (spikes.SPIKE_PASS_DTYPE, one per recorded
+        pass) and ``raster`` (u32 dst; spikes.split cuts it into passes)."""
+        info = _lib.SpikesInfo()
+        call("abnn_spikes_get_info", self._h, C.byref(info))
+        passes = np.zeros(int(info.passes_recorded), dtype=_spikes.SPIKE_PASS_DTYPE)
+        call("abnn_spikes_read_passes", self._h, 0, passes.shape[0], _ptr(passes))
+        cfg = getattr(self, "_spk", None)
+        raster = np.zeros(int(info.spikes_recorded) if cfg is not None and cfg.raster_capacity else 0, dtype=np.uint32)
+        call("abnn_spikes_read_raster", self._h, 0, raster.shape[0], _ptr(raster))
+        return {"info": info.as_dict(), "passes": passes, "raster": raster}
+
+    def spike_counts(self, first: Optional[int] = None, n: Optional[int] = None) -> np.ndarray:
+        """Per-neuron spike counts (u32) of the absolute neuron ids [first,
+        first + n); by default the whole selected range."""
+        cfg = getattr(self, "_spk", None)
+        lo, cnt = (cfg.first, cfg.count) if cfg is not None and cfg.count else (0, self.n_neuron())
+        first = lo if first is None else int(first)
+        n = lo + cnt - first if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=np.uint32)
+        call("abnn_spikes_read_counts", self._h, first, n, _ptr(out))
+        return out
+
+    def clear_spikes(self, keep_counts: bool = False) -> None:
+        """Empty the pass table and the raster and re-arm recording."""
+        call("abnn_spikes_clear", self._h, 1 if keep_counts else 0)
+
+    def stop_spikes(self) -> None:
+        """Free the recorder (synchronises)."""
+        self._spk = None
+        call("abnn_spikes_stop", self._h)
 
     # ---- neuron state ---------------------------------------------------------------------------
     def last_fired(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:

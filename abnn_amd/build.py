@@ -5,6 +5,7 @@
 * ``build_cpp_example()`` : g++ -> tests/cpp/brain_cpp_test (C++ Brain API over the C-ABI)
 * ``build_learn_test()``  : g++ -> tests/cpp/learn_test (device-resident learning loop vs the oracle)
 * ``build_census_test()`` : g++ -> tests/cpp/census_test (the synapse census's C++ mirrors)
+* ``build_spikes_test()`` : g++ -> tests/cpp/spikes_test (the spike recorder's C++ mirrors, the engine path)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -19,9 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "abnn_amd")
 CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
-               os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip")]
+               os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
-                          os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"),
+                          os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -36,6 +37,8 @@ LEARN_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "learn_test.cpp")
 LEARN_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "learn_test")
 CENSUS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "census_test.cpp")
 CENSUS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "census_test")
+SPIKES_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "spikes_test.cpp")
+SPIKES_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "spikes_test")
 LEARN_BENCH_SRC = os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -188,6 +191,13 @@ def build_census_test(force: bool = False) -> str | None:
     return CENSUS_TEST_BIN
 
 
+def build_spikes_test(force: bool = False) -> str | None:
+    """Test program of the spike recorder's C++ mirrors (Brain::record_spikes ...
+    against the oracle's per-pass lists) and of the recorder inside the
+    device-resident learning loop against the host-driven loop."""
+    return _build_with_oracle(SPIKES_TEST_SRC, SPIKES_TEST_BIN, force)
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -208,6 +218,7 @@ def build_all(force: bool = False) -> None:
     build_engine_tests(force)
     build_learn_test(force)
     build_census_test(force)
+    build_spikes_test(force)
     build_learn_bench(force)
 
 

@@ -19,6 +19,7 @@
 #include "census.h"
 #include "engine.h"
 #include "learn.h"
+#include "spikes.h"
 
 using namespace abnn;
 
@@ -99,6 +100,7 @@ struct abnn_brain {
     uint64_t idx_cap = 0;
     uint64_t* u64_scratch = nullptr;
     uint64_t* census_out = nullptr;  // abnn_census's device result (allocated by its first call)
+    SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
     uint64_t rot = 0;              // passes run by this handle: the bitmap buffers' rotation (never reset)
@@ -169,7 +171,8 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
+                    b->u64_scratch,  b->census_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
@@ -627,6 +630,13 @@ abnn_status run_shard_fused_gate(abnn_brain* b, int32_t* xchg, hipStream_t s)
 abnn_status run_commit(abnn_brain* b, const int32_t* gathered, uint32_t world, bool renorm,
                        hipStream_t s)
 {
+    // the spike recorder: this pass's list, with the mirrors' values before the tick, the +1 and the renormalisation
+    if (b->spikes.on) {
+        const uint64_t slot = b->pass_host & (kFiredRing - 1);
+        HIP_TRY(launch_spike_record(b->spikes, b->d.fired_ring + slot * (uint64_t)b->params.max_spikes,
+                                    b->d.n_fired_ring + slot, b->params.max_spikes, b->pass_host, b->clock_host,
+                                    (uint32_t)b->renorms, s));
+    }
     host_tick(b);
     // sharded passes write the merged spike list into fired_ring too
     b->clean_passes += 1;
@@ -1130,6 +1140,116 @@ abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* 
     HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, *cfg, scale, b->census_out, (uint32_t)b->cus, b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->census_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+/* ---- spike recorder (spikes.hip) --------------------------- */
+
+namespace {
+
+void spikes_free(abnn_brain* b)
+{
+    SpikeRecorder& r = b->spikes;
+    void* ptrs[] = {r.words, r.passes, r.raster, r.counts};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    r = SpikeRecorder{};
+}
+
+constexpr const char* kNoRecorder = "abnn_spikes: the handle has no recorder (abnn_spikes_start)";
+
+}  // namespace
+
+abnn_status abnn_spikes_start(abnn_brain* b, const abnn_spikes_config* cfg)
+{
+    REQUIRE(b && cfg, "null argument");
+    ST_TRY(sync_all(b));  // launches of a running recorder write its buffers
+    spikes_free(b);
+    REQUIRE(cfg->reserved[0] == 0 && cfg->reserved[1] == 0 && cfg->counts <= 1,
+            "abnn_spikes_start: reserved must be 0, counts 0 or 1");
+    REQUIRE(cfg->pass_capacity >= 1, "abnn_spikes_start: pass_capacity must be at least 1");
+    REQUIRE(!cfg->count || (uint64_t)cfg->first + cfg->count <= b->n_nrn, "abnn_spikes_start: the range ends above N_NRN");
+    SpikeRecorder& r = b->spikes;
+    r.cfg = *cfg;
+    r.first = cfg->count ? cfg->first : 0u;
+    r.n_counts = cfg->counts ? (cfg->count ? (uint64_t)cfg->count : b->n_nrn) : 0;
+    abnn_status st = dalloc(&r.words, kSpikeWords);
+    if (st == ABNN_OK) st = dalloc(&r.passes, cfg->pass_capacity);
+    if (st == ABNN_OK && cfg->raster_capacity) st = dalloc(&r.raster, cfg->raster_capacity);
+    if (st == ABNN_OK && r.n_counts) st = dalloc(&r.counts, r.n_counts);
+    if (st != ABNN_OK) {
+        spikes_free(b);
+        return st;
+    }
+    HIP_TRY(hipDeviceSynchronize());  // the buffers' zeros
+    r.on = true;
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_stop(abnn_brain* b)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(b->spikes.on, kNoRecorder);
+    ST_TRY(sync_all(b));
+    spikes_free(b);
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_clear(abnn_brain* b, int keep_counts)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(b->spikes.on, kNoRecorder);
+    ST_TRY(sync_all(b));
+    SpikeRecorder& r = b->spikes;
+    HIP_TRY(hipMemset(r.words + 3, 0, (kSpikeWords - 3) * sizeof(uint64_t)));  // recorded, dropped, the flag
+    if (!keep_counts && r.counts) HIP_TRY(hipMemset(r.counts, 0, r.n_counts * sizeof(uint32_t)));
+    HIP_TRY(hipDeviceSynchronize());
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_get_info(abnn_brain* b, abnn_spikes_info* out)
+{
+    REQUIRE(b && out, "null argument");
+    REQUIRE(b->spikes.on, kNoRecorder);
+    ST_TRY(sync_all(b));
+    HIP_TRY(hipMemcpy(out, b->spikes.words, sizeof(*out), hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_read_passes(abnn_brain* b, uint64_t first, uint64_t n, abnn_spike_pass* out)
+{
+    REQUIRE(b && (out || n == 0), "null argument");
+    REQUIRE(b->spikes.on, kNoRecorder);
+    abnn_spikes_info info{};
+    ST_TRY(abnn_spikes_get_info(b, &info));
+    REQUIRE(first <= info.passes_recorded && n <= info.passes_recorded - first,
+            "abnn_spikes_read_passes: beyond the recorded passes");
+    if (n) HIP_TRY(hipMemcpy(out, b->spikes.passes + first, n * sizeof(*out), hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_read_raster(abnn_brain* b, uint64_t first, uint64_t n, uint32_t* out)
+{
+    REQUIRE(b && (out || n == 0), "null argument");
+    REQUIRE(b->spikes.on, kNoRecorder);
+    abnn_spikes_info info{};
+    ST_TRY(abnn_spikes_get_info(b, &info));
+    const uint64_t have = b->spikes.raster ? info.spikes_recorded : 0;
+    REQUIRE(first <= have && n <= have - first, "abnn_spikes_read_raster: beyond the recorded spikes");
+    if (n) HIP_TRY(hipMemcpy(out, b->spikes.raster + first, n * sizeof(*out), hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_read_counts(abnn_brain* b, uint64_t first_neuron, uint64_t n, uint32_t* out)
+{
+    REQUIRE(b && (out || n == 0), "null argument");
+    const SpikeRecorder& r = b->spikes;
+    REQUIRE(r.on, kNoRecorder);
+    REQUIRE(r.counts, "abnn_spikes_read_counts: the recorder keeps no counts");
+    REQUIRE(first_neuron >= r.first && first_neuron - r.first <= r.n_counts && n <= r.n_counts - (first_neuron - r.first),
+            "abnn_spikes_read_counts: neurons outside the selected range");
+    ST_TRY(sync_all(b));
+    if (n) HIP_TRY(hipMemcpy(out, r.counts + (first_neuron - r.first), n * sizeof(*out), hipMemcpyDeviceToHost));
     return ABNN_OK;
 }
 

@@ -357,6 +357,18 @@ class ShardedBrain:
         words = np.concatenate([counts[:6], bits.astype(np.uint64), counts[6:]])
         return _census.decode(words, cfg)
 
+    def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
+        """Brain.record_spikes on the local handle.  No collective: every
+        rank's spike list is the merged global one, so any rank's recorder
+        holds the whole network's spikes."""
+        self.brain.record_spikes(raster, passes, neurons, counts)
+
+    def spikes(self) -> dict:
+        return self.brain.spikes()
+
+    def spike_counts(self, first=None, n=None) -> np.ndarray:
+        return self.brain.spike_counts(first, n)
+
     def local_events(self) -> int:
         return self.brain.visited_events()
 

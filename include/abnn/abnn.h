@@ -317,6 +317,80 @@ abnn_status abnn_census_enqueue(abnn_brain* b, const abnn_census_config* cfg, ui
 /* Synchronous convenience: out_host holds `words` u64 (== abnn_census_words(cfg)). */
 abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_host, uint64_t words);
 
+/* ---- spike recorder -----------------------------------------
+ * A recorder attached to a handle.  While it is on, every pass the handle
+ * completes (abnn_traverse, the passes inside abnn_engine_run, abnn_shard_commit
+ * / abnn_shard_traverse) enqueues one small launch, in stream order after the
+ * pass's kernels, that appends the pass's spikes to device buffers.  Nothing
+ * synchronises and nothing returns to the host; with the recorder off a pass
+ * enqueues exactly what it enqueued before.
+ * For one pass, L is its spike list: the dst of every spike the traversal
+ * emitted, in global budget order -- exactly the sequence of lastFired[dst] =
+ * now stamps of schedule C1.  |L| is the pass's increment of abnn_stats.fired;
+ * a dst may occur many times.  Stamps written by the host or by the learning
+ * loop's boundary kernel (abnn_inject_inputs, teacher forcing,
+ * abnn_set_timestamps / abnn_set_last_fired, the auto-stimulus) are not spikes
+ * of the traversal and are not in L.  S is the subsequence of L whose dst lies
+ * in [first, first + count), or all of L when count == 0, in the same order.
+ * Per pass:
+ *   - passes_seen += 1, spikes_seen += |L|, selected_seen += |S|;
+ *   - with counts: counts[d - first] += 1 (u32) for every entry d of S -- over
+ *     every pass since the start, dropped ones included;
+ *   - the pass is RECORDED iff no earlier pass was dropped since the start or
+ *     the last clear, the pass table has a free entry, and raster_capacity == 0
+ *     or spikes_recorded + |S| <= raster_capacity.  A recorded pass appends its
+ *     abnn_spike_pass entry (offset = spikes_recorded before it), with a raster
+ *     also S as u32 dst, and adds 1 / |S| to passes_recorded / spikes_recorded;
+ *   - otherwise it is DROPPED whole (passes_dropped += 1, spikes_dropped +=
+ *     |S|), and so is every later pass until a clear: the recorded passes are
+ *     always the first K consecutive ones and the raster never holds part of a
+ *     pass.
+ * Every word is an integer, so the result does not depend on the launch shape
+ * (abnn_amd/spikes.py restates the rule in numpy).  A shard handle is accepted:
+ * every rank's spike list is the merged global one, so any rank's recorder
+ * holds the whole network's spikes.                                           */
+typedef struct abnn_spikes_config {      /* 32 bytes */
+    uint64_t raster_capacity;   /* spikes the raster holds; 0 = keep no raster (pass table and counts only) */
+    uint32_t pass_capacity;     /* pass entries held, >= 1 */
+    uint32_t first, count;      /* count 0 = every neuron; else only dst in [first, first + count) */
+    uint32_t counts;            /* 1: keep per-neuron spike counts over the selected neurons */
+    uint32_t reserved[2];       /* 0 */
+} abnn_spikes_config;
+typedef struct abnn_spike_pass {         /* 32 bytes, one per recorded pass */
+    uint64_t pass_index;        /* abnn_scalars.pass_index the pass ran as (before its +1) */
+    uint64_t now;               /* the pass-start clock = the value its stamps wrote */
+    uint64_t offset;            /* its first raster entry */
+    uint32_t count;             /* |S| */
+    uint32_t epoch;             /* abnn_renormalisations before the pass (low 32 bits) */
+} abnn_spike_pass;
+typedef struct abnn_spikes_info {        /* u64 words; host view after a synchronise */
+    uint64_t passes_seen, spikes_seen, selected_seen;   /* since start: passes, sum |L|, sum |S| */
+    uint64_t passes_recorded, spikes_recorded;           /* since start or the last clear */
+    uint64_t passes_dropped, spikes_dropped;             /* since start or the last clear; spikes = sum |S| of dropped passes */
+} abnn_spikes_info;
+/* Allocates and zeroes the recorder's buffers and synchronises; a second call
+ * restarts (the old recorder is freed first).  ABNN_ERR_INVALID: a null
+ * argument, reserved != 0, counts > 1, pass_capacity == 0, a range that ends
+ * above N_NRN.  ABNN_ERR_OOM: an allocation failed.  A failed start leaves no
+ * recorder (one that was running is stopped) and the handle usable.          */
+abnn_status abnn_spikes_start(abnn_brain* b, const abnn_spikes_config* cfg);
+/* Synchronises and frees.  abnn_brain_destroy frees too.  Every function below
+ * (and this one) returns ABNN_ERR_INVALID when the handle has no recorder.    */
+abnn_status abnn_spikes_stop(abnn_brain* b);
+/* Synchronises, empties the pass table and the raster and re-arms recording:
+ * the *_recorded and *_dropped words restart at 0, the *_seen words go on.
+ * keep_counts == 0 also zeroes the per-neuron counts.                         */
+abnn_status abnn_spikes_clear(abnn_brain* b, int keep_counts);
+/* The readers synchronise first, like every state accessor.  A read beyond
+ * what is recorded is ABNN_ERR_INVALID: passes [first, first + n) within
+ * passes_recorded; raster entries within spikes_recorded (any n > 0 without a
+ * raster); counts for the ABSOLUTE neuron ids [first_neuron, first_neuron + n)
+ * inside the selected range (every neuron when count == 0), counts on.        */
+abnn_status abnn_spikes_get_info(abnn_brain* b, abnn_spikes_info* out);
+abnn_status abnn_spikes_read_passes(abnn_brain* b, uint64_t first, uint64_t n, abnn_spike_pass* out);
+abnn_status abnn_spikes_read_raster(abnn_brain* b, uint64_t first, uint64_t n, uint32_t* out);
+abnn_status abnn_spikes_read_counts(abnn_brain* b, uint64_t first_neuron, uint64_t n, uint32_t* out);
+
 /* ---- neuron timestamps / scalars ----------------------------------------- */
 abnn_status abnn_get_last_fired(abnn_brain* b, uint64_t first, uint64_t* out, uint64_t n);
 abnn_status abnn_set_last_fired(abnn_brain* b, uint64_t first, const uint64_t* src, uint64_t n);

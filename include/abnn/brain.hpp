@@ -364,6 +364,36 @@ public:
         check(abnn_census(h_, &cfg, w.data(), abnn_census_words(&cfg)), "abnn_census");
         return Census::from_words(w.data(), cfg.bins);
     }
+    // The spike recorder (abnn_spikes_*; the contract is in abnn.h): from
+    // record_spikes on, every pass appends its spike list to device buffers.
+    void record_spikes(const abnn_spikes_config& cfg) { check(abnn_spikes_start(h_, &cfg), "abnn_spikes_start"); }
+    abnn_spikes_info spikes_info() const
+    {
+        abnn_spikes_info i{};
+        check(abnn_spikes_get_info(h_, &i), "abnn_spikes_get_info");
+        return i;
+    }
+    // every recorded pass / the whole raster / the counts of the selected neurons
+    std::vector<abnn_spike_pass> read_spike_passes() const
+    {
+        std::vector<abnn_spike_pass> p(spikes_info().passes_recorded);
+        check(abnn_spikes_read_passes(h_, 0, p.size(), p.data()), "abnn_spikes_read_passes");
+        return p;
+    }
+    std::vector<uint32_t> read_spike_raster(uint64_t first, uint64_t n) const
+    {
+        std::vector<uint32_t> r(n);
+        check(abnn_spikes_read_raster(h_, first, n, r.data()), "abnn_spikes_read_raster");
+        return r;
+    }
+    std::vector<uint32_t> read_spike_counts(uint64_t first_neuron, uint64_t n) const
+    {
+        std::vector<uint32_t> c(n);
+        check(abnn_spikes_read_counts(h_, first_neuron, n, c.data()), "abnn_spikes_read_counts");
+        return c;
+    }
+    void clear_spikes(bool keep_counts = false) { check(abnn_spikes_clear(h_, keep_counts ? 1 : 0), "abnn_spikes_clear"); }
+    void stop_spikes() { check(abnn_spikes_stop(h_), "abnn_spikes_stop"); }
     abnn_brain* handle() const { return h_; }
     // Before a caller changes the device state through handle() (the
     // device-resident learning loop, engine.hpp): pending Shared-view writes

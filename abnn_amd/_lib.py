@@ -143,6 +143,19 @@ class CensusConfig(C.Structure):
     ]
 
 
+DEG_OUT, DEG_IN, DEG_OUT_W, DEG_IN_W = 1, 2, 4, 8
+DEGREE_HEADER_WORDS = 8
+
+
+class DegreeConfig(C.Structure):
+    """abnn_degree_config -- the neuron range (count 0 = every neuron) and the planes of a degree census."""
+
+    _fields_ = [
+        ("first", C.c_uint32), ("count", C.c_uint32), ("what", C.c_uint32),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
 class SpikesConfig(C.Structure):
     """abnn_spikes_config -- the spike recorder's capacities, neuron range (count 0 = every neuron) and counts switch."""
 
@@ -227,6 +240,9 @@ SIGNATURES = [
     ("abnn_census_words", C.c_uint64, [C.POINTER(CensusConfig)]),
     ("abnn_census_enqueue", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _VP]),
     ("abnn_census", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _U64]),
+    ("abnn_degree_words", C.c_uint64, [C.POINTER(DegreeConfig), _U64]),
+    ("abnn_degree_enqueue", C.c_int, [_VP, C.POINTER(DegreeConfig), _VP, _VP]),
+    ("abnn_degree", C.c_int, [_VP, C.POINTER(DegreeConfig), _VP, _U64]),
     ("abnn_spikes_start", C.c_int, [_VP, C.POINTER(SpikesConfig)]),
     ("abnn_spikes_stop", C.c_int, [_VP]),
     ("abnn_spikes_clear", C.c_int, [_VP, C.c_int]),
@@ -298,7 +314,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_census_words", "abnn_census_enqueue", "abnn_census", "abnn_engine_set_census",
                    "abnn_engine_census_count", "abnn_engine_read_census",
                    "abnn_spikes_start", "abnn_spikes_stop", "abnn_spikes_clear", "abnn_spikes_get_info",
-                   "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts")
+                   "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts",
+                   "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree")
 
 _lib = None
 

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import census as _census
+from . import degree as _degree
 from . import spikes as _spikes
 from ._lib import Dims, Params, Scalars, State, Stats, call
 
@@ -177,6 +178,26 @@ class Brain:
         """Enqueue a census into device memory at ``out_ptr`` (abnn_census_words(cfg)
         u64) on ``stream``; nothing synchronises.  Decode with census.decode."""
         call("abnn_census_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
+
+    def degrees(self, neurons=None, what=("out", "in", "out_w", "in_w")) -> dict:
+        """Neuron degree census on the device (abnn_degree): per
+        neuron of ``neurons`` = (first, count) (None: every neuron) the live
+        records that leave it (``out``) and enter it (``in``), np.uint64, and
+        their weights' sums in 2**-24 fixed point (``out_w`` / ``in_w``,
+        np.int64), for the planes named in ``what``; the definition is in
+        abnn.h.  Returns the header counts and the planes (degree.decode)."""
+        cfg = _degree.config(neurons, what)
+        n_nrn = self.n_neuron()
+        words = int(self._lib.abnn_degree_words(C.byref(cfg), n_nrn))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_degree", self._h, C.byref(cfg), _ptr(out), words)  # an invalid config fails here
+        return _degree.decode(out, cfg, n_nrn)
+
+    def degrees_enqueue(self, cfg: _lib.DegreeConfig, out_ptr: int, stream=None) -> None:
+        """Enqueue a degree census into device memory at ``out_ptr``
+        (abnn_degree_words(cfg, N_NRN) u64) on ``stream``; nothing synchronises.
+        Decode with degree.decode."""
+        call("abnn_degree_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
 
     # ---- spike recorder (abnn_spikes_*, DESIGN.md §9) -------------------------------------------
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:

@@ -6,6 +6,7 @@
 * ``build_learn_test()``  : g++ -> tests/cpp/learn_test (device-resident learning loop vs the oracle)
 * ``build_census_test()`` : g++ -> tests/cpp/census_test (the synapse census's C++ mirrors)
 * ``build_spikes_test()`` : g++ -> tests/cpp/spikes_test (the spike recorder's C++ mirrors, the engine path)
+* ``build_degree_test()`` : g++ -> tests/cpp/degree_test (the degree census's C++ mirrors)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -20,9 +21,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "abnn_amd")
 CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
-               os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip")]
+               os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
+               os.path.join(CSRC, "degree.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
+                          os.path.join(CSRC, "degree.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -39,7 +42,9 @@ CENSUS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "census_test.cpp")
 CENSUS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "census_test")
 SPIKES_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "spikes_test.cpp")
 SPIKES_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "spikes_test")
-LEARN_BENCH_SRC = os.path.join(ROOT, "tools", "learn_bench.cpp")
+DEGREE_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "degree_test.cpp")
+DEGREE_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "degree_test")
+LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
@@ -198,6 +203,20 @@ def build_spikes_test(force: bool = False) -> str | None:
     return _build_with_oracle(SPIKES_TEST_SRC, SPIKES_TEST_BIN, force)
 
 
+def build_degree_test(force: bool = False) -> str | None:
+    """Test program of the degree census's C++ mirrors (Brain::degrees,
+    DegreeView vs a host loop over the downloaded records)."""
+    if not os.path.exists(DEGREE_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [DEGREE_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(DEGREE_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", DEGREE_TEST_BIN, DEGREE_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return DEGREE_TEST_BIN
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -219,6 +238,7 @@ def build_all(force: bool = False) -> None:
     build_learn_test(force)
     build_census_test(force)
     build_spikes_test(force)
+    build_degree_test(force)
     build_learn_bench(force)
 
 

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "census.h"
+#include "degree.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -100,6 +101,8 @@ struct abnn_brain {
     uint64_t idx_cap = 0;
     uint64_t* u64_scratch = nullptr;
     uint64_t* census_out = nullptr;  // abnn_census's device result (allocated by its first call)
+    uint64_t* degree_out = nullptr;  // abnn_degree's device result, grown to the largest one asked
+    uint64_t degree_cap = 0;
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
@@ -171,7 +174,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->u64_scratch,  b->census_out, b->degree_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -1139,6 +1142,52 @@ abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* 
     if (!b->census_out) ST_TRY(dalloc(&b->census_out, ABNN_CENSUS_HEADER_WORDS + ABNN_CENSUS_MAX_BINS));
     HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, *cfg, scale, b->census_out, (uint32_t)b->cus, b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->census_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+/* ---- neuron degree census (degree.hip) ---------------------- */
+
+uint64_t abnn_degree_words(const abnn_degree_config* cfg, uint64_t n_nrn) { return degree_words(cfg, n_nrn); }
+
+namespace {
+
+abnn_status degree_check(const abnn_brain* b, const abnn_degree_config* cfg)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(degree_config_ok(cfg, b->n_nrn, nullptr),
+            "degree: what must be a non-empty subset of the four planes, reserved 0, count 0 only with first 0, "
+            "first + count <= N_NRN");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_degree_enqueue(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(degree_check(b, cfg));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(launch_degree(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, out_dev, (uint32_t)b->cus, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(degree_check(b, cfg));
+    REQUIRE(words == degree_words(cfg, b->n_nrn), "abnn_degree: words must equal abnn_degree_words(cfg, N_NRN)");
+    ST_TRY(sync_all(b));
+    if (words > b->degree_cap) {
+        if (b->degree_out) (void)hipFree(b->degree_out);
+        b->degree_out = nullptr;
+        b->degree_cap = 0;
+        ST_TRY(dalloc(&b->degree_out, words));
+        b->degree_cap = words;
+    }
+    HIP_TRY(launch_degree(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->degree_out, (uint32_t)b->cus, b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->degree_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return ABNN_OK;
 }

@@ -357,6 +357,21 @@ class ShardedBrain:
         words = np.concatenate([counts[:6], bits.astype(np.uint64), counts[6:]])
         return _census.decode(words, cfg)
 
+    def degrees(self, neurons=None, what=("out", "in", "out_w", "in_w")) -> dict:
+        """Brain.degrees over every shard's records (collective: every rank
+        calls it at the same point and gets the whole graph's result): the
+        local result, then the header counts and the planes summed as int64
+        (all_reduce_sum; the strength planes wrap as the device's sums do)."""
+        from . import degree as _degree
+
+        torch = self._torch
+        cfg = _degree.config(neurons, what)
+        n_nrn = self.brain.n_neuron()
+        local = _degree.to_words(self.brain.degrees(neurons, what))
+        t = torch.from_numpy(local.view(np.int64).copy()).to(self.xchg.device)
+        self.comm.all_reduce_sum(t)  # words 6 / 7 are zeros on every rank
+        return _degree.decode(t.cpu().numpy().view(np.uint64), cfg, n_nrn)
+
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
         """Brain.record_spikes on the local handle.  No collective: every
         rank's spike list is the merged global one, so any rank's recorder

@@ -317,6 +317,54 @@ abnn_status abnn_census_enqueue(abnn_brain* b, const abnn_census_config* cfg, ui
 /* Synchronous convenience: out_host holds `words` u64 (== abnn_census_words(cfg)). */
 abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* out_host, uint64_t words);
 
+/* ---- neuron degree census -----------------------------------
+ * One streaming pass over the handle's local records [0, n_syn): per neuron of
+ * a range R = [first, first + M) (M = count, or N_NRN when count == 0), the
+ * number of live records that leave it (src == n) and that enter it (dst == n)
+ * and the fixed-point sums of their weights, without moving the records to the
+ * host.  A tombstone (dst == 0xFFFFFFFF) counts in no plane; records past n_syn
+ * are never read.
+ * Strength.  A weight is SUMMABLE iff fabsf(w) < 128.0f (false for NaN and
+ * +-inf); its term is q = (int32_t)(w * 16777216.0f): one fp32 multiply (exact)
+ * and a truncation toward zero (denormals give 0).  A strength plane holds the
+ * two's-complement 64-bit sum of the terms modulo 2^64: strength = (int64_t)word
+ * / 2^24.  A record that is not summable adds nothing to the strength plane, 1
+ * to the skipped word and 1 to the degree plane.
+ * Every word is an integer sum, so the result is the same for any grid and
+ * order (abnn_amd/degree.py restates it in numpy).
+ * Result: ABNN_DEGREE_HEADER_WORDS + P * M u64 words, P = the bits set in what:
+ *   0 records scanned (= n_syn)   1 tombstones among them
+ *   2 live records with src in R (0 unless OUT or OUT_W is asked)
+ *   3 live records with dst in R (0 unless IN or IN_W is asked)
+ *   4 records of word 2 that are not summable (0 unless OUT_W is asked)
+ *   5 likewise for word 3 (0 unless IN_W is asked)          6, 7 zero
+ *   8... one plane of M words per bit asked, in increasing bit order; word j
+ *        of a plane belongs to neuron first + j.
+ * Word 2 is the sum of the OUT plane and word 3 of the IN plane, when asked.  */
+#define ABNN_DEG_OUT   1u   /* plane: live records with src == n (fan-out)            */
+#define ABNN_DEG_IN    2u   /* plane: live records with dst == n (fan-in)             */
+#define ABNN_DEG_OUT_W 4u   /* plane: fixed-point sum of w over records with src == n */
+#define ABNN_DEG_IN_W  8u   /* plane: ... with dst == n                               */
+#define ABNN_DEGREE_HEADER_WORDS 8
+typedef struct abnn_degree_config {
+    uint32_t first, count;   /* neurons [first, first+count); count 0 = every neuron (first must be 0) */
+    uint32_t what;           /* non-empty subset of the four bits above */
+    uint32_t reserved[5];    /* 0 */
+} abnn_degree_config;         /* 32 bytes */
+/* The result's words for a brain of n_nrn neurons, or 0 for an invalid config:
+ * null, what == 0 or a bit above 15, a reserved word that is not 0, count == 0
+ * with first != 0, first + count > n_nrn, n_nrn == 0.                          */
+uint64_t abnn_degree_words(const abnn_degree_config* cfg, uint64_t n_nrn);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, abnn_degree_words(cfg,
+ * N_NRN) u64) in stream order on `stream`; no synchronise, so it can sit
+ * between passes.  A shard handle counts its own records.  ABNN_ERR_INVALID: a
+ * null argument, a config that is invalid for the handle's N_NRN, a handle
+ * whose records are invalid.  n_syn == 0 is valid: all-zero planes.           */
+abnn_status abnn_degree_enqueue(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_degree_words(cfg,
+ * N_NRN)).  Its device scratch stays with the handle until abnn_brain_destroy. */
+abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* out_host, uint64_t words);
+
 /* ---- spike recorder -----------------------------------------
  * A recorder attached to a handle.  While it is on, every pass the handle
  * completes (abnn_traverse, the passes inside abnn_engine_run, abnn_shard_commit

@@ -70,6 +70,37 @@ struct Census {
     }
 };
 
+// A view of a degree census result (abnn.h abnn_degree: the header and one
+// plane of `count` words per bit of `what`); it does not own the words.
+struct DegreeView {
+    const uint64_t* words = nullptr;
+    uint32_t what = 0;
+    uint64_t count = 0;  // neurons of the range
+    DegreeView(const uint64_t* w, const abnn_degree_config& cfg, uint64_t n_nrn)
+        : words(w), what(cfg.what), count(cfg.count ? cfg.count : n_nrn)
+    {
+    }
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }
+    uint64_t out_total() const { return words[2]; }
+    uint64_t in_total() const { return words[3]; }
+    uint64_t out_skipped() const { return words[4]; }
+    uint64_t in_skipped() const { return words[5]; }
+    // the plane of one bit (ABNN_DEG_*): `count` words, or nullptr when it was not asked
+    const uint64_t* plane(uint32_t bit) const
+    {
+        if (!(what & bit)) return nullptr;
+        uint64_t before = 0;
+        for (uint32_t b = 1; b < bit; b <<= 1) before += (what & b) ? 1 : 0;
+        return words + ABNN_DEGREE_HEADER_WORDS + before * count;
+    }
+    const uint64_t* out() const { return plane(ABNN_DEG_OUT); }
+    const uint64_t* in() const { return plane(ABNN_DEG_IN); }
+    // the strength planes as two's-complement sums: strength = value / 2^24
+    const int64_t* out_w() const { return reinterpret_cast<const int64_t*>(plane(ABNN_DEG_OUT_W)); }
+    const int64_t* in_w() const { return reinterpret_cast<const int64_t*>(plane(ABNN_DEG_IN_W)); }
+};
+
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
@@ -363,6 +394,20 @@ public:
         std::vector<uint64_t> w(abnn_census_words(&cfg) ? abnn_census_words(&cfg) : 1);
         check(abnn_census(h_, &cfg, w.data(), abnn_census_words(&cfg)), "abnn_census");
         return Census::from_words(w.data(), cfg.bins);
+    }
+    // Neuron degree census on the device (abnn_degree; the definition is in
+    // abnn.h): the result's words, to be read through a DegreeView.
+    std::vector<uint64_t> degrees(const abnn_degree_config& cfg) const
+    {
+        const uint64_t words = abnn_degree_words(&cfg, n_neuron());
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_degree(h_, &cfg, w.data(), words), "abnn_degree");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_degree_words(&cfg, n_neuron()) u64.
+    void degrees_enqueue(const abnn_degree_config& cfg, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_degree_enqueue(h_, &cfg, out_dev, stream), "abnn_degree_enqueue");
     }
     // The spike recorder (abnn_spikes_*; the contract is in abnn.h): from
     // record_spikes on, every pass appends its spike list to device buffers.

@@ -7,12 +7,13 @@ this package is its Python host mirror:
 * :class:`LearnEngine` -- the device-resident learning loop (``abnn_engine_*``);
 * :mod:`abnn_amd.census` -- the synapse census: config, numpy reference, merge of shard results;
 * :mod:`abnn_amd.degree` -- the neuron degree census: config, numpy reference, merge of shard results;
+* :mod:`abnn_amd.select` -- the synapse select: config, numpy reference, merge of shard results;
 * :mod:`abnn_amd.spikes` -- the spike recorder: config, pass dtype, numpy reference, raster split;
 * :mod:`abnn_amd.shard` -- synapse-shard data parallelism over torch.distributed;
 * :mod:`abnn_amd.configs` -- the BASELINE.json workloads.
 """
-from . import census, degree, spikes
-from ._lib import (AbnnError, CensusConfig, DegreeConfig, SpikesConfig, default_params, device_count,
+from . import census, degree, select, spikes
+from ._lib import (AbnnError, CensusConfig, DegreeConfig, SelectConfig, SpikesConfig, default_params, device_count,
                    load as load_library)
 from .brain import SYN_DTYPE, Brain, visited_events
 from .configs import CONFIGS, Workload
@@ -21,6 +22,6 @@ from .spikes import SPIKE_PASS_DTYPE
 
 __all__ = [
     "AbnnError", "Brain", "CONFIGS", "CensusConfig", "DegreeConfig", "LearnEngine", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
-    "SpikesConfig", "Workload", "default_engine_config", "census", "default_params", "degree", "device_count",
-    "load_library", "spikes", "visited_events",
+    "SelectConfig", "SpikesConfig", "Workload", "default_engine_config", "census", "default_params", "degree",
+    "device_count", "load_library", "select", "spikes", "visited_events",
 ]

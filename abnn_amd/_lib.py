@@ -156,6 +156,21 @@ class DegreeConfig(C.Structure):
     ]
 
 
+SELECT_ANY, SELECT_WEIGHT = 1, 2
+SELECT_HEADER_WORDS = 8
+
+
+class SelectConfig(C.Structure):
+    """abnn_select_config -- the src / dst ranges (count 0 = not set), the weight bounds and the flags of a select."""
+
+    _fields_ = [
+        ("src_first", C.c_uint32), ("src_count", C.c_uint32),
+        ("dst_first", C.c_uint32), ("dst_count", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("flags", C.c_uint32), ("reserved", C.c_uint32),
+    ]
+
+
 class SpikesConfig(C.Structure):
     """abnn_spikes_config -- the spike recorder's capacities, neuron range (count 0 = every neuron) and counts switch."""
 
@@ -243,6 +258,9 @@ SIGNATURES = [
     ("abnn_degree_words", C.c_uint64, [C.POINTER(DegreeConfig), _U64]),
     ("abnn_degree_enqueue", C.c_int, [_VP, C.POINTER(DegreeConfig), _VP, _VP]),
     ("abnn_degree", C.c_int, [_VP, C.POINTER(DegreeConfig), _VP, _U64]),
+    ("abnn_select_words", C.c_uint64, [C.POINTER(SelectConfig), _U64]),
+    ("abnn_select_enqueue", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _VP]),
+    ("abnn_select", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _U64]),
     ("abnn_spikes_start", C.c_int, [_VP, C.POINTER(SpikesConfig)]),
     ("abnn_spikes_stop", C.c_int, [_VP]),
     ("abnn_spikes_clear", C.c_int, [_VP, C.c_int]),
@@ -315,7 +333,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_engine_census_count", "abnn_engine_read_census",
                    "abnn_spikes_start", "abnn_spikes_stop", "abnn_spikes_clear", "abnn_spikes_get_info",
                    "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts",
-                   "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree")
+                   "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree",
+                   "abnn_select_words", "abnn_select_enqueue", "abnn_select")
 
 _lib = None
 

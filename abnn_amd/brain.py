@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib
 from . import census as _census
 from . import degree as _degree
+from . import select as _select
 from . import spikes as _spikes
 from ._lib import Dims, Params, Scalars, State, Stats, call
 
@@ -198,6 +199,34 @@ class Brain:
         (abnn_degree_words(cfg, N_NRN) u64) on ``stream``; nothing synchronises.
         Decode with degree.decode."""
         call("abnn_degree_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
+
+    def select(self, src=None, dst=None, weights=None, any: bool = False, capacity: Optional[int] = None) -> dict:
+        """Synapse select on the device (abnn_select): this
+        handle's records that match, in record order.  ``src`` / ``dst`` are
+        (first, count) neuron ranges (None = not set), ``weights`` = (w_lo,
+        w_hi) keeps w_lo <= w < w_hi, ``any`` matches either set range instead
+        of both; the rule is in abnn.h.  At most ``capacity`` matches are
+        returned; None first counts (capacity 0) and then selects exactly the
+        matches.  Returns records, tombstones, matched, written, syn_offset,
+        capacity, ``index`` (np.uint64, global) and ``syn`` (SYN_DTYPE), both
+        trimmed to written (select.decode)."""
+        cfg = _select.config(src, dst, weights, any)
+        if capacity is None:
+            capacity = self._select(cfg, 0)["matched"]
+        return self._select(cfg, int(capacity))
+
+    def _select(self, cfg: _lib.SelectConfig, capacity: int) -> dict:
+        words = int(self._lib.abnn_select_words(C.byref(cfg), capacity))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_select", self._h, C.byref(cfg), capacity, _ptr(out), words)  # an invalid config fails here
+        return _select.decode(out, capacity)
+
+    def select_enqueue(self, cfg: _lib.SelectConfig, capacity: int, out_ptr: int, stream=None) -> None:
+        """Enqueue a select into device memory at ``out_ptr``
+        (abnn_select_words(cfg, capacity) u64) on ``stream``; nothing
+        synchronises after the handle's first select.  Plane entries at and
+        past ``written`` are not written.  Decode with select.decode."""
+        call("abnn_select_enqueue", self._h, C.byref(cfg), int(capacity), int(out_ptr), _stream_ptr(stream))
 
     # ---- spike recorder (abnn_spikes_*, DESIGN.md §9) -------------------------------------------
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:

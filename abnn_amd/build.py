@@ -7,6 +7,7 @@
 * ``build_census_test()`` : g++ -> tests/cpp/census_test (the synapse census's C++ mirrors)
 * ``build_spikes_test()`` : g++ -> tests/cpp/spikes_test (the spike recorder's C++ mirrors, the engine path)
 * ``build_degree_test()`` : g++ -> tests/cpp/degree_test (the degree census's C++ mirrors)
+* ``build_select_test()`` : g++ -> tests/cpp/select_test (the synapse select's C++ mirrors)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -22,10 +23,10 @@ PKG = os.path.join(ROOT, "abnn_amd")
 CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
-               os.path.join(CSRC, "degree.hip")]
+               os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
-                          os.path.join(CSRC, "degree.h"),
+                          os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -44,6 +45,8 @@ SPIKES_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "spikes_test.cpp")
 SPIKES_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "spikes_test")
 DEGREE_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "degree_test.cpp")
 DEGREE_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "degree_test")
+SELECT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "select_test.cpp")
+SELECT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "select_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -217,6 +220,20 @@ def build_degree_test(force: bool = False) -> str | None:
     return DEGREE_TEST_BIN
 
 
+def build_select_test(force: bool = False) -> str | None:
+    """Test program of the synapse select's C++ mirrors (Brain::select,
+    SelectView vs a host loop over the downloaded records)."""
+    if not os.path.exists(SELECT_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [SELECT_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(SELECT_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", SELECT_TEST_BIN, SELECT_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return SELECT_TEST_BIN
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -239,6 +256,7 @@ def build_all(force: bool = False) -> None:
     build_census_test(force)
     build_spikes_test(force)
     build_degree_test(force)
+    build_select_test(force)
     build_learn_bench(force)
 
 

@@ -18,6 +18,7 @@
 
 #include "census.h"
 #include "degree.h"
+#include "select.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -103,6 +104,8 @@ struct abnn_brain {
     uint64_t* census_out = nullptr;  // abnn_census's device result (allocated by its first call)
     uint64_t* degree_out = nullptr;  // abnn_degree's device result, grown to the largest one asked
     uint64_t degree_cap = 0;
+    SelectScratch select;            // abnn_select_*: per-tile counts and offsets for syn_capacity (its first call)
+    uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
@@ -174,7 +177,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->degree_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -968,6 +971,8 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     if ((s = dalloc(&d.range_bounds_next, max_ranges + 1)) != ABNN_OK) return fail(s);
     if ((s = dalloc(&d.range_bounds_prev, max_ranges + 1)) != ABNN_OK) return fail(s);
     d.adapt_ranges = std::getenv("ABNN_STATIC_RANGES") ? 0u : 1u;
+    b->select_blocks = 4u * (uint32_t)std::max(1, b->cus);  // 32 waves per CU, as the census
+    if (const char* env = std::getenv("ABNN_SELECT_BLOCKS")) b->select_blocks = (uint32_t)std::max(1, std::atoi(env));
     if ((s = reset_ranges(b)) != ABNN_OK) return fail(s);
     *out = b;
     return ABNN_OK;
@@ -1189,6 +1194,80 @@ abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* 
     HIP_TRY(launch_degree(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->degree_out, (uint32_t)b->cus, b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->degree_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+/* ---- synapse select (select.hip) ---------------------------- */
+
+uint64_t abnn_select_words(const abnn_select_config* cfg, uint64_t capacity) { return select_words(cfg, capacity); }
+
+namespace {
+
+// The checks of a select on handle b, then its scratch (the first call
+// allocates it: that one may synchronise the device).
+abnn_status select_check(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(select_words(cfg, capacity) != 0,
+            "select: unknown flags, reserved != 0, w_lo / w_hi without WEIGHT, a NaN bound or w_lo >= w_hi, "
+            "ANY with no range set, or a range that wraps u32");
+    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= b->n_nrn, "select: src range ends above N_NRN");
+    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= b->n_nrn, "select: dst range ends above N_NRN");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // no memset: a select zeroes the counts it reads and writes the offsets it reads
+    if (!b->select.counts)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->select.counts),
+                          std::max<uint64_t>(4, select_count_words(b->dims.syn_capacity)) * sizeof(uint32_t)));
+    if (!b->select.offsets)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->select.offsets),
+                          std::max<uint64_t>(1, select_tiles(b->dims.syn_capacity)) * sizeof(uint64_t)));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_select_enqueue(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_dev,
+                                void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(select_check(b, cfg, capacity));
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_select(b->d.syn, b->dims.n_syn, b->dims.syn_offset, *cfg, capacity, b->select, out_dev,
+                          b->select_blocks, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_host,
+                        uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(select_check(b, cfg, capacity));
+    REQUIRE(words == select_words(cfg, capacity), "abnn_select: words must equal abnn_select_words(cfg, capacity)");
+    ST_TRY(sync_all(b));
+    // the device result lives for this call only: a capacity of every record is 24 B per record
+    uint64_t* dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(uint64_t));
+    if (e != hipSuccess) {
+        set_err(std::string("abnn_select: hipMalloc(") + std::to_string(words * sizeof(uint64_t)) + " B): " +
+                hipGetErrorString(e));
+        return ABNN_ERR_OOM;
+    }
+    e = launch_select(b->d.syn, b->dims.n_syn, b->dims.syn_offset, *cfg, capacity, b->select, dev, b->select_blocks,
+                      b->stream);
+    const uint64_t h = ABNN_SELECT_HEADER_WORDS;
+    if (e == hipSuccess) e = hipMemcpyAsync(out_host, dev, h * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    const uint64_t written = e == hipSuccess ? out_host[3] : 0;
+    if (e == hipSuccess && written) {  // the header, then only the entries that were written
+        e = hipMemcpyAsync(out_host + h, dev + h, written * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(out_host + h + capacity, dev + h + capacity, written * sizeof(abnn_synapse),
+                               hipMemcpyDeviceToHost, b->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    }
+    (void)hipFree(dev);
+    HIP_TRY(e);
     return ABNN_OK;
 }
 

@@ -24,7 +24,7 @@ the clock back over unmerged visits.
 """
 from __future__ import annotations
 
-from typing import Protocol
+from typing import Optional, Protocol
 
 import numpy as np
 
@@ -371,6 +371,49 @@ class ShardedBrain:
         t = torch.from_numpy(local.view(np.int64).copy()).to(self.xchg.device)
         self.comm.all_reduce_sum(t)  # words 6 / 7 are zeros on every rank
         return _degree.decode(t.cpu().numpy().view(np.uint64), cfg, n_nrn)
+
+    def select(self, src=None, dst=None, weights=None, any: bool = False, capacity: Optional[int] = None) -> dict:
+        """Brain.select over every shard's records (collective: every rank
+        calls it at the same point and gets the whole graph's result, indices
+        global).  The local count, the header counts exchanged (all_reduce_sum
+        and all_gather of every rank's matches), the local select of what the
+        merged result needs from this rank, one all_gather of the planes padded
+        to the largest part, then select.merge in rank order."""
+        from . import select as _select
+
+        torch, dev = self._torch, self.xchg.device
+        head = self.brain.select(src, dst, weights, any, capacity=0)
+        t_sum = torch.tensor([head["records"], head["tombstones"], head["matched"]], dtype=torch.int64, device=dev)
+        self.comm.all_reduce_sum(t_sum)
+        mine = torch.tensor([head["matched"]], dtype=torch.int64, device=dev)
+        every = torch.zeros(self.world, dtype=torch.int64, device=dev)
+        self.comm.all_gather(every, mine)
+        matched = [int(m) for m in every.cpu().tolist()]
+        capacity = int(t_sum[2].item()) if capacity is None else int(capacity)
+        # what the merged result takes from each rank: the first `capacity` matches in rank order
+        take, need = [], capacity
+        for m in matched:
+            take.append(min(m, need))
+            need -= take[-1]
+        local = self.brain.select(src, dst, weights, any, capacity=take[self.rank])
+        pad = max(max(take), 1)
+        plane = np.zeros(3 * pad, dtype=np.int64)  # index plane, then record plane
+        plane[:local["written"]] = local["index"].view(np.int64)
+        plane[pad:pad + 2 * local["written"]] = local["syn"].view(np.int64)
+        t_in = torch.from_numpy(plane).to(dev)
+        t_out = torch.zeros(self.world * 3 * pad, dtype=torch.int64, device=dev)
+        self.comm.all_gather(t_out, t_in)
+        planes = t_out.cpu().numpy().reshape(self.world, 3 * pad)
+        parts = []
+        for r in range(self.world):
+            n = take[r]
+            parts.append({"records": 0, "tombstones": 0, "matched": matched[r], "written": n,
+                          "syn_offset": 0,  # the whole graph's
+                          "index": planes[r, :n].view(np.uint64),
+                          "syn": np.ascontiguousarray(planes[r, pad:pad + 2 * n]).view(_select.SYN_DTYPE)})
+        out = _select.merge(parts, capacity)
+        out["records"], out["tombstones"] = int(t_sum[0].item()), int(t_sum[1].item())
+        return out
 
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
         """Brain.record_spikes on the local handle.  No collective: every

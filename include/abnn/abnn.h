@@ -365,6 +365,65 @@ abnn_status abnn_degree_enqueue(abnn_brain* b, const abnn_degree_config* cfg, ui
  * N_NRN)).  Its device scratch stays with the handle until abnn_brain_destroy. */
 abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* out_host, uint64_t words);
 
+/* ---- synapse select ------------------------------------------
+ * An ordered stream compaction of the handle's local records [0, n_syn): the
+ * records that MATCH, in increasing record order and with their indices, into a
+ * caller-sized buffer, without moving the other records to the host.  Records
+ * past n_syn are never read.
+ * Matching rule (every comparison one u32 or IEEE fp32 operation; abnn_amd/
+ * select.py restates it in numpy).  A tombstone (dst == 0xFFFFFFFF) never
+ * matches.  S is src - src_first < src_count and D is dst - dst_first <
+ * dst_count, in u32.  Without ABNN_SELECT_ANY a range that is not set (count 0)
+ * is true and the range test is S && D; with it a range that is not set is
+ * false and the test is S || D (ANY with neither range set is invalid).  With
+ * ABNN_SELECT_WEIGHT the record must also satisfy w >= w_lo && w < w_hi: NaN
+ * never matches; the bounds are not NaN, w_lo < w_hi, +-inf are allowed.
+ * Result, as u64 words (abnn_select_words = 8 + 3 * capacity):
+ *   0 records scanned (= n_syn)   1 tombstones among them
+ *   2 matched: every matching record, whatever the capacity
+ *   3 written = min(matched, capacity)   4 the handle's syn_offset   5..7 zero
+ *   8 ...             the index plane: capacity u64; entry k = syn_offset +
+ *                     the local index of the k-th match in index order
+ *   8 + capacity ...  the record plane: capacity abnn_synapse (16 B each);
+ *                     entry k is that record {src, dst, w, pad = 0}, the bits
+ *                     of w unchanged
+ * The first `capacity` matches in index order are written.  Plane entries at
+ * and past `written` are NOT written (only the header is zeroed), so a large
+ * buffer costs no memset.  capacity == 0 is a pure count (8 words).  The result
+ * does not depend on the grid or on timing.                                   */
+#define ABNN_SELECT_ANY     1u  /* a record matches when EITHER set range holds (neighbourhood); default: every set range holds */
+#define ABNN_SELECT_WEIGHT  2u  /* also require w_lo <= w && w < w_hi */
+#define ABNN_SELECT_HEADER_WORDS 8
+typedef struct abnn_select_config {      /* 32 bytes */
+    uint32_t src_first, src_count;       /* count 0 = range not set */
+    uint32_t dst_first, dst_count;
+    float    w_lo, w_hi;                 /* read only with ABNN_SELECT_WEIGHT; else both must be +0.0f */
+    uint32_t flags;
+    uint32_t reserved;                   /* 0 */
+} abnn_select_config;
+/* 8 + 3 * capacity, or 0 for an invalid config (whatever can be checked without
+ * a handle): null, unknown flag bits, reserved != 0, a non-zero w_lo or w_hi
+ * without WEIGHT, a NaN bound or w_lo >= w_hi with it, ANY with neither range
+ * set, a range whose first + count exceeds 2^32.                               */
+uint64_t    abnn_select_words(const abnn_select_config* cfg, uint64_t capacity);
+/* Enqueue only: three launches in stream order on `stream` (count per tile of
+ * records, prefix over the tiles, emit) that fill out_dev (DEVICE memory,
+ * abnn_select_words(cfg, capacity) u64); no workgroup waits for another and
+ * nothing synchronises, so it can sit between passes.  A shard handle selects
+ * its own records; its indices are global through syn_offset.
+ * The handle owns the select's scratch (per-tile counts and offsets, sized for
+ * syn_capacity): the FIRST select call on a handle allocates it and may
+ * synchronise the device; abnn_brain_destroy frees it.  Because the scratch is
+ * per handle, two selects of one handle enqueued on different streams must be
+ * ordered by the caller (an event, or one stream).
+ * ABNN_ERR_INVALID: a null argument, an invalid config, a range that ends above
+ * N_NRN, a handle whose records are invalid.  n_syn == 0 is valid.            */
+abnn_status abnn_select_enqueue(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_select_words(cfg,
+ * capacity)); the header and only the first `written` entries of each plane are
+ * copied, the rest of out_host is left untouched.                             */
+abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_host, uint64_t words);
+
 /* ---- spike recorder -----------------------------------------
  * A recorder attached to a handle.  While it is on, every pass the handle
  * completes (abnn_traverse, the passes inside abnn_engine_run, abnn_shard_commit

@@ -101,6 +101,26 @@ struct DegreeView {
     const int64_t* in_w() const { return reinterpret_cast<const int64_t*>(plane(ABNN_DEG_IN_W)); }
 };
 
+// A view of a select result (abnn.h abnn_select: the header, the index plane
+// and the record plane of `capacity` entries each, the first written() of them
+// valid); it does not own the words.
+struct SelectView {
+    const uint64_t* words = nullptr;
+    uint64_t capacity = 0;
+    SelectView(const uint64_t* w, uint64_t cap) : words(w), capacity(cap) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }
+    uint64_t matched() const { return words[2]; }
+    uint64_t written() const { return words[3]; }
+    uint64_t syn_offset() const { return words[4]; }
+    // entry k < written(): the global index of the k-th match, and the record
+    const uint64_t* index() const { return words + ABNN_SELECT_HEADER_WORDS; }
+    const abnn_synapse* syn() const
+    {
+        return reinterpret_cast<const abnn_synapse*>(words + ABNN_SELECT_HEADER_WORDS + capacity);
+    }
+};
+
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
@@ -408,6 +428,22 @@ public:
     void degrees_enqueue(const abnn_degree_config& cfg, uint64_t* out_dev, void* stream = nullptr) const
     {
         check(abnn_degree_enqueue(h_, &cfg, out_dev, stream), "abnn_degree_enqueue");
+    }
+    // Synapse select on the device (abnn_select; the rule is in abnn.h): the
+    // result's words for at most `capacity` matches, to be read through a
+    // SelectView.  The plane entries at and past written() stay zero.
+    std::vector<uint64_t> select(const abnn_select_config& cfg, uint64_t capacity) const
+    {
+        const uint64_t words = abnn_select_words(&cfg, capacity);
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_select(h_, &cfg, capacity, w.data(), words), "abnn_select");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_select_words(&cfg, capacity) u64.
+    void select_enqueue(const abnn_select_config& cfg, uint64_t capacity, uint64_t* out_dev,
+                        void* stream = nullptr) const
+    {
+        check(abnn_select_enqueue(h_, &cfg, capacity, out_dev, stream), "abnn_select_enqueue");
     }
     // The spike recorder (abnn_spikes_*; the contract is in abnn.h): from
     // record_spikes on, every pass appends its spike list to device buffers.

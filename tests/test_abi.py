@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from high_id_helpers import _code_src, _src_code
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "abnn", "abnn.h")
 DEBUG_HEADER = os.path.join(ROOT, "include", "abnn", "abnn_debug.h")
@@ -120,24 +122,6 @@ def test_shard_partition_helpers():
     assert global_events(1_000_000_000, 150_000_000, 1) == 150_000_128
     assert global_events(1_000_000_000, 150_000_000, 8) == 1_000_000_000
     assert global_events(1_000_000_000, 150_000_000, 2) == 2 * 150_000_128
-
-
-def _src_code(n):
-    """abnn.h (abnn_state): the filter code of a 24-bit src, as (lo, hi)."""
-    n = n.astype(np.uint64)
-    b, j = n & 31, (n >> 5) & 0x7FFFF
-    jh = j >> 13
-    t = jh * 0x9E5
-    g, hb = (j ^ t) & 8191, (b + t) & 31
-    return (g << 3 | (hb & 7)), (b | (jh >> 5) << 5 | (hb >> 3) << 6)
-
-
-def _code_src(lo, hi):
-    g, b = lo >> 3, hi & 31
-    hb = (lo & 7) | (hi >> 6) << 3
-    jh = (((hb - b) * 13) & 31) | ((hi >> 5) & 1) << 5
-    j = ((g ^ jh * 0x9E5) & 8191) | jh << 13
-    return j << 5 | b
 
 
 def test_src_code_is_a_bijection_matching_the_filter():

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+from high_id_helpers import _bitmap, _expected_bitmap, recent_mask
 from shard_helpers import GpuShards, oracle_shard_pass
 
 pytestmark = pytest.mark.gpu
@@ -412,24 +413,6 @@ def test_config3_full_size_parity(gpu):
     assert st_g == st_o
 
 
-def _bitmap(g):
-    import ctypes as C
-    nw = 2 * ((g.n_neuron() + 63) // 64)
-    out = np.zeros(nw, dtype=np.uint32)
-    inc = C.c_int(0)
-    f = g._lib.abnn_debug_bitmap
-    f.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_int)]
-    f.restype = C.c_int
-    assert f(g._h, out.ctypes.data, nw, C.byref(inc)) == 0
-    return out, bool(inc.value)
-
-
-def _expected_bitmap(last_fired_at_start, now, n_words, window=5):
-    bits = ((np.uint64(now) - last_fired_at_start.astype(np.uint64)) <= np.uint64(window)).astype(np.uint8)
-    bits = np.concatenate([bits, np.zeros(n_words * 32 - bits.size, np.uint8)])
-    return np.packbits(bits.reshape(-1, 32)[:, ::-1], axis=1).view(">u4").ravel().astype(np.uint32)
-
-
 def test_recent_bitmap_update_with_host_writes(gpu):
     """The steady-state bitmap (built by k_apply from the last passes' spike
     lists) against the bitmap recomputed from lastFired every pass, and the
@@ -466,3 +449,44 @@ def test_recent_bitmap_update_with_host_writes(gpu):
         _assert_same(g, o, f"pass {k}")
     assert all(modes[5:12]) and all(modes[28:]), modes  # built by k_apply before and after the writes
     assert not any(modes[12:17]) and not any(modes[18:28]), modes
+
+
+def test_handle_path_across_a_clock_of_2_to_the_32(gpu):
+    """Ages are u32 (age32): the handle path across a clock of 2^32, every pass
+    against the oracle and the exact bitmap against the one recomputed with
+    u32 ages.  Neurons never stamped (lastFired = 0) are recent again at
+    clocks 2^32 .. 2^32 + 5.  The spike-list bitmap build needs clock + W <
+    2^32 (capi.hip build_next_ok) and, after a set_scalars, W - 1 passes of
+    spike lists: a set_scalars straight to 2^32 - 9 would leave it no pass in
+    which both hold, so the clock is set ten passes earlier and the twenty
+    passes start when it reaches 2^32 - 9."""
+    W = 5
+    g, o = _pair(99_488, 1_000_000, 1_000_000, renorm_thresh=2**64 - 1)
+    for x in (g, o):
+        sc = x.scalars()
+        x.set_scalars(2**32 - 19, sc["reward"], sc["rbar"], sc["pass_index"])
+    modes, clocks, all_recent = [], [], 0
+    for k in range(-10, 20):
+        now = g.scalars()["clock"]
+        assert now == 2**32 - 9 + k
+        lf0 = g.last_fired()
+        lf0[:256] = now  # the stimulus is stamped at pass start
+        g.encode_traversal(1)
+        o.pass_threaded(nthreads=16)
+        bm, inc_next = _bitmap(g)
+        modes.append(inc_next)
+        clocks.append(now)
+        want = _expected_bitmap(lf0, now, bm.size)
+        never = recent_mask(lf0, now)[lf0 == 0]  # (the oracle says so: it is compared below)
+        if never.size:
+            back = 2**32 <= now <= 2**32 + W
+            assert never.all() if back else not never.any(), f"clock {now}"
+            all_recent += back
+        assert np.array_equal(bm, want), f"bitmap, clock {now}"
+        _assert_same(g, o, f"clock {now}")
+    assert g.stats() == o.stats()
+    assert all_recent == W + 1  # the never-stamped neurons were there to come back
+    guard = [c + W < 2**32 for c in clocks]
+    assert any(m for m, ok in zip(modes, guard) if ok), modes  # built from the spike lists before ...
+    assert not any(m for m, ok in zip(modes, guard) if not ok), modes  # ... and by k_bitmap from there on
+    assert guard[10 + 3] and not guard[10 + 4]

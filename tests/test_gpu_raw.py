@@ -108,7 +108,8 @@ class RawBrain:
 
 
 def _run(n_hidden, n_syn, events, passes, seed=1, max_spikes=2560, reward_at=None, tombstones=0, renorm_at=None,
-         clock0=0, knobs=None, pool_chunks=None, threads=0):
+         clock0=0, knobs=None, pool_chunks=None, threads=0, syn=None):
+    """syn: explicit records over 512 + n_hidden neurons (else the generated graph of `seed`)."""
     from oracle import oracle as O
 
     n_nrn = 512 + n_hidden
@@ -116,7 +117,11 @@ def _run(n_hidden, n_syn, events, passes, seed=1, max_spikes=2560, reward_at=Non
     over["max_spikes"] = max_spikes
     over["renorm_thresh"] = 2**64 - 1  # the raw launcher's host decides renormalisation (renorm_at below)
     o = O.OracleBrain(256, 256, n_hidden, n_syn, events, **over)
-    o.build_random_graph(seed, nthreads=max(8, threads))
+    if syn is None:
+        o.build_random_graph(seed, nthreads=max(8, threads))
+    else:
+        assert len(syn) == n_syn
+        o.set_synapses(syn)
     if tombstones:  # pruned records {0xFFFFFFFF, 0xFFFFFFFF} (abnn.h): never pass
         idx = np.arange(0, n_syn, max(1, n_syn // tombstones))[:tombstones]
         s = o.syn.copy()
@@ -267,3 +272,20 @@ def test_raw_workspace_reused_across_sizes(gpu):
         assert np.array_equal(r.last_fired(), (o.last_fired & np.uint64(0xFFFFFFFF)).astype(np.uint32)), k
         assert np.array_equal(r.records(), o.syn.view(np.uint32)), k
         assert r.workspace_error() == 0, k
+
+
+@pytest.mark.parametrize("n_nrn", [2**24 - 2, 2**25 + 77], ids=["all-24-bit-ids", "ids-above-24-bits"])
+def test_raw_high_ids_every_pass(gpu, n_nrn):
+    """The launcher's own filter (raw_t, k_raw_filter's H fold levels) on the
+    crafted graph of tests/high_id_helpers.py: every id class n >> 18 holds
+    recent probes and aliasing decoys -- 64 classes at 2^24 - 2 neurons, 129
+    (H = 129, ids the handle path does not admit) at 2^25 + 77."""
+    from high_id_helpers import CLASS_LOG2, high_id_graph, high_id_parts
+
+    parts = high_id_parts(n_nrn)
+    assert np.unique(parts["probes"] >> CLASS_LOG2).size == (n_nrn - 1 >> CLASS_LOG2) + 1
+    assert len(parts["decoys"]) >= 40
+    syn = high_id_graph(n_nrn)
+    o = _run(n_nrn - 512, len(syn), len(syn), 8, reward_at=4, threads=16, syn=syn)
+    st = o.stats()
+    assert st["fired"] > 0 and st["updated"] > st["fired"]

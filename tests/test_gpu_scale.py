@@ -2,9 +2,11 @@
 synapses, 150M events per pass) -- the HIP pass against the threaded C oracle,
 bit-exact, after 80 passes from the freshly built graph (into the steady state).
 
-Sizes the small parity tests never reach are exercised here: neuron ids above
-2^18 (the pre-spike filter's block hash and rotation, engine.h / kernels.hip),
-thousands of ranges and workgroups, the adaptive partition, the candidate lists
+Sizes the small parity tests never reach are exercised here: thousands of
+ranges and workgroups at once with neuron ids above 2^18 (the pre-spike
+filter's block hash and rotation, engine.h / kernels.hip; those ids alone, up
+to 2^24 - 2, run in seconds on a crafted 1M-record graph in
+tests/test_gpu_high_ids.py), the adaptive partition, the candidate lists
 of dense ranges, the budget cut far inside the sweep.  The sweep touches only
 the first E = 150M records, so the oracle holds exactly those (the generator is
 per-record, bench.py cpu_baseline does the same): lastFired of every neuron,

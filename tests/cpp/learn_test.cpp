@@ -7,7 +7,7 @@
 // step, windows.  The GPU side runs the passes in uneven chunks with no
 // synchronise between the calls (handle A); the call-boundary values need a
 // synchronise, so they are read on a second handle (B) run with the same chunks.
-//   usage: learn_test CASE   (1..5, tests/test_learn_gpu.py; prints one JSON line)
+//   usage: learn_test CASE   (1..7, tests/test_learn_gpu.py; prints one JSON line)
 #include <abnn/brain.hpp>
 #include <abnn/engine.hpp>
 
@@ -42,6 +42,7 @@ struct Case {
     abnn::EngineConfig cfg;
     uint64_t renorm_thresh;  // 0: the default
     bool hand_back;
+    void (*knobs)(abnn_params&) = nullptr;  // brain knobs off the defaults
 };
 
 Case make_case(int id)
@@ -67,6 +68,31 @@ Case make_case(int id)
         case 5:  // hand-back to the host paths after 40 engine passes
             c.passes = 40;
             c.hand_back = true;
+            break;
+        case 6:  // off the default knobs: a clock that skips, the widest incremental window, weights above 1
+            // (with clock_inc = 2 read_outputs' window [now - 1, now) can hold no stamp: the loop
+            // and the host driver must agree on that as on everything else)
+            c.passes = 120;
+            c.cfg.win_size = 30;
+            c.renorm_thresh = 50;
+            c.knobs = [](abnn_params& p) {
+                p.clock_inc = 2;
+                p.window_pre = 7;
+                p.tick_ns = 500;
+                p.w_max = 2.0f;
+            };
+            break;
+        case 7:  // no earlier spike list in the window, a reward term that moves the weights
+            c.passes = 120;
+            c.cfg.win_size = 30;
+            c.renorm_thresh = 50;
+            c.knobs = [](abnn_params& p) {
+                p.clock_inc = 1;
+                p.window_pre = 1;
+                p.tick_ns = 500;
+                p.w_max = 2.0f;
+                p.eta_reward = 0.5f;
+            };
             break;
         default: std::fprintf(stderr, "unknown case %d\n", id); std::exit(2);
     }
@@ -129,6 +155,7 @@ int main(int argc, char** argv)
     abnn_params params;
     abnn_default_params(&params);
     if (c.renorm_thresh) params.renorm_thresh = c.renorm_thresh;
+    if (c.knobs) c.knobs(params);
 
     abnn::Brain gpu_a(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params);
     abnn::Brain gpu_b(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params);

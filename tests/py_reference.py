@@ -27,7 +27,11 @@ def rand01(s: int) -> np.float32:
 
 
 def metal_clamp(x, lo, hi):
-    return min(max(x, lo), hi)
+    """Metal's clamp(x, lo, hi) = fmin(fmax(x, lo), hi): a NaN x gives lo.
+    Written as the two selects of csrc/device.h clampf (Python's max / min
+    would return the NaN)."""
+    m = x if x > lo else lo
+    return m if m < hi else hi
 
 
 class Cell:

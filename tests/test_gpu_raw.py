@@ -12,6 +12,8 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import knob_helpers as K
+
 pytestmark = pytest.mark.gpu
 
 
@@ -194,6 +196,25 @@ def test_raw_knobs(gpu):
 
     k = _lib.default_params(base_scale=1.7, refractory=0, window_pre=2, eta_home=1e-4, a_ltp=0.08, w_min=0.05)
     _run(9_488, 100_000, 100_000, 8, knobs=k, reward_at=2)
+
+
+@pytest.mark.parametrize("name", list(K.RAW_KNOBS))
+def test_raw_knobs_off_the_defaults(gpu, name):
+    """tests/knob_helpers.py RAW_KNOBS: a clock that skips, the edges of
+    window_pre, a refractory gate that passes nothing, and the w_min / w_max
+    buffer arguments crossed and at 0 / 2 (tests/test_knob_model.py asserts
+    that each case stays busy)."""
+    from abnn_amd import _lib
+
+    _run(*K.RAW, 8, knobs=_lib.default_params(**K.RAW_KNOBS[name]), reward_at=2)
+
+
+@pytest.mark.parametrize("pool_chunks", [None, 0], ids=["pool", "no-pool"])
+def test_raw_special_weights(gpu, pool_chunks):
+    """Weights that are NaN, infinite, zero, subnormal, negative and above 1
+    through the launcher's update sites; without a survivor pool every
+    survivor is recomputed from its record (k_raw_apply)."""
+    _run(*K.RAW, 8, reward_at=4, pool_chunks=pool_chunks, syn=K.graph(K.RAW, seed=1, special=True))
 
 
 @pytest.mark.parametrize("pool_chunks", [0, 3, 4200])

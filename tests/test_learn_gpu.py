@@ -59,6 +59,27 @@ def test_hand_back_to_the_host_paths(gpu):
     assert res["passes"] == 40 and res["spikes"] > 0
 
 
+@pytest.mark.gpu
+def test_clock_inc_2_window_pre_7(gpu):
+    """Off the default knobs (clock_inc = 2, window_pre = 7, tick_ns = 500,
+    w_max = 2, renormalisation every ~25 passes).  With the clock skipping,
+    read_outputs' window [now - 1, now) holds no stamp: what is asserted is
+    that the device loop and the host driver agree on that (the program's
+    bit-for-bit comparison), not that the trace holds spikes."""
+    res = _run_case(6)
+    assert res["passes"] == 120 and res["windows"] == 4
+    assert res["teacher_stamps"] > 0
+    assert res["renorms_gpu"] == res["renorms_cpu"] and res["renorms_cpu"] >= 1
+
+
+@pytest.mark.gpu
+def test_window_pre_1_with_a_large_reward_term(gpu):
+    res = _run_case(7)
+    assert res["passes"] == 120 and res["windows"] == 4
+    assert res["spikes"] > 0 and res["reward_changes"] > 0 and res["teacher_stamps"] > 0
+    assert res["renorms_gpu"] == res["renorms_cpu"] and res["renorms_cpu"] >= 1
+
+
 def _stimulus(frames, n_in=256, n_out=256, dt=0.0009, hz=0.5):
     """FunctionalDataset's frames (functional-dataset.cpp:24-52) as test_engine._frames
     makes them, vectorised: cos^2 input, 0.5 sin + 0.5 target, libm's cosf / sinf."""

@@ -50,6 +50,14 @@ SELECT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "select_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
+# kernels.hip: uniform regions keep their own control flow.  The gate's stream
+# loop chooses between two flavours of its record loads with a scalar branch
+# (engine.h pin_k); structurized, that if / else becomes two ifs in a row,
+# the compiler no longer knows how many loads are in flight past them, and the
+# loop waits for all of them every iteration (s_waitcnt vmcnt(0) where the
+# plain diamond gets vmcnt(5)).
+SOURCE_FLAGS = {"kernels.hip": ["-mllvm", "-structurizecfg-skip-uniform-regions"]}
+
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 HIP_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
              "-ffp-contract=off", "-Wall", "-Werror=return-type", "-ldl"]
@@ -91,7 +99,7 @@ def build_hip(force: bool = False, out: str | None = None, defines: list[str] | 
         for src in HIP_SOURCES:
             obj = f"{target}.{os.path.basename(src)}.o"
             objs.append(obj)
-            cmd = [HIPCC, *comp, *(defines or []), "-c", "-o", obj, src]
+            cmd = [HIPCC, *comp, *SOURCE_FLAGS.get(os.path.basename(src), []), *(defines or []), "-c", "-o", obj, src]
             procs.append((cmd, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)))
         errs = []
         for cmd, p in procs:

@@ -362,6 +362,17 @@ abnn_status time_begin(abnn_brain* b, hipStream_t s, EventPair** out)
     return ABNN_OK;
 }
 
+// Bytes of the sweep's record stream kept in the Infinity Cache from pass to
+// pass (ABNN_STREAM_PIN_MB, MiB; 0 = none: every stream load non-temporal).
+// profiles/ab_stream_pin.txt has the sweep over it.
+constexpr uint64_t kStreamPinMiB = 160;  // config 3: 5 of 16, the best of the sweep
+uint64_t stream_pin_bytes()
+{
+    uint64_t mib = kStreamPinMiB;
+    if (const char* env = std::getenv("ABNN_STREAM_PIN_MB")) mib = (uint64_t)std::min(4096, std::max(0, std::atoi(env)));
+    return mib << 20;
+}
+
 // Sweep partition for the current record count: visited events, wave
 // iterations and the persistent gate grid (one range per wave).  Run at
 // creation and after every structural update.
@@ -379,6 +390,13 @@ void configure(abnn_brain* b)
     if (G == 0 && iters > 0) G = 1;
     d.gate_blocks = (uint32_t)G;
     d.n_ranges = (uint32_t)(G * waves);  // <= kMaxGateBlocks * 16 = kMaxRanges
+    // the slice of the 3 B/event record stream that fits the budget, in
+    // sixteenths of the sweep (engine.h pin_k): config 3's 450 MB get 5 of 16
+    // at 160 MiB, the full sweep's 3 GB none
+    const uint64_t budget = stream_pin_bytes();
+    d.pin_k = 0;
+    if (d.events > 0 && b->params.mode == ABNN_MODE_SWEEP && !b->params.track_visits)
+        d.pin_k = (uint32_t)std::min<uint64_t>(16, 16 * budget / (3 * d.events));
 }
 
 // Uniform sweep partition: range r starts at iteration floor(r * iters / NR)
@@ -2104,6 +2122,15 @@ abnn_status abnn_debug_range_bounds(abnn_brain* b, uint32_t* out, uint64_t n)
     REQUIRE(b && out, "null argument");
     ST_TRY(sync_all(b));
     HIP_TRY(hipMemcpy(out, b->d.range_bounds, std::min<uint64_t>(n, b->d.n_ranges + 1ull) * 4, hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+// Diagnostics (not part of abnn.h): the stream's pinned slice in use, in
+// sixteenths of the sweep (engine.h pin_k).
+abnn_status abnn_debug_stream_pin(abnn_brain* b, uint32_t* pin_k)
+{
+    REQUIRE(b && pin_k, "null argument");
+    *pin_k = b->d.pin_k;
     return ABNN_OK;
 }
 

@@ -167,6 +167,9 @@ struct DeviceState {
     uint32_t chunk_penalty;   // partition cost added per full chunk, 40-ns units (ABNN_CHUNK_PENALTY)
     uint32_t apply_blocks;    // k_claim / k_apply grid (<= kWalkBlocks; ABNN_APPLY_BLOCKS)
     uint32_t range_map;       // gate wave -> range: 0 blocked (workgroup b: ranges b*NW..), 1 interleaved (ABNN_RANGE_MAP=1)
+    uint32_t pin_k;           // sweep: iterations with (index & 15) < pin_k are read with ordinary loads and so stay in
+                              // the Infinity Cache between passes, the others non-temporal (0..16; capi.hip
+                              // configure from ABNN_STREAM_PIN_MB; 0 with track_visits and in random mode)
     // fused pass: look-back words [gate_blocks]; gate costs of the previous
     // pass (read by the prologue when prologue_adapt) and of this one
     uint64_t* lb_status;

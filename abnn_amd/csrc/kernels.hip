@@ -1455,10 +1455,27 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
                                    : reinterpret_cast<const u32x4*>(d.dummy);
             const u32x2* bh = live ? reinterpret_cast<const u32x2*>(d.syn.hi) + it * (IE / 8)
                                    : reinterpret_cast<const u32x2*>(d.dummy);
+            // The stream's pinned slice (engine.h pin_k): iterations whose
+            // index mod 16 is below pin_k -- the same lines every pass -- are
+            // read with ordinary loads and stay in the Infinity Cache from one
+            // pass to the next; the rest stays non-temporal and passes them
+            // by (tools/ubench_slice.hip).  Wave-uniform: one scalar branch.
+            // (the asm comments keep the two flavours apart: without them the
+            // compiler merges the branches into one pair of ordinary loads)
+            if (((uint32_t)it & 15u) < d.pin_k) {
+                asm volatile("; pinned");
 #pragma unroll
-            for (int b = 0; b < NB8; ++b) {
-                x.lo[b] = __builtin_nontemporal_load(bl + b * 64 + lane);
-                x.hi[b] = __builtin_nontemporal_load(bh + b * 64 + lane);
+                for (int b = 0; b < NB8; ++b) {
+                    x.lo[b] = bl[b * 64 + lane];
+                    x.hi[b] = bh[b * 64 + lane];
+                }
+                asm volatile("; pinned end");
+            } else {
+#pragma unroll
+                for (int b = 0; b < NB8; ++b) {
+                    x.lo[b] = __builtin_nontemporal_load(bl + b * 64 + lane);
+                    x.hi[b] = __builtin_nontemporal_load(bh + b * 64 + lane);
+                }
             }
             if constexpr (kTrack) {  // dst of the same events: 8 {dst, w} pairs per lane and block
                 const u32x4* bd = reinterpret_cast<const u32x4*>(live ? reinterpret_cast<const uint32_t*>(d.syn.dw + (uint64_t)it * IE)

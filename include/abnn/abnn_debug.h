@@ -32,6 +32,9 @@ abnn_status abnn_debug_apply_clock(abnn_brain* b, uint64_t* out, uint64_t n);
 abnn_status abnn_debug_bitmap(abnn_brain* b, uint32_t* out, uint64_t n, int* incremental_next);
 /* The current sweep partition: n_ranges + 1 iteration bounds. */
 abnn_status abnn_debug_range_bounds(abnn_brain* b, uint32_t* out, uint64_t n);
+/* The pinned slice of the sweep's record stream in use: iterations whose index
+ * mod 16 is below *pin_k are read with ordinary loads (ABNN_STREAM_PIN_MB). */
+abnn_status abnn_debug_stream_pin(abnn_brain* b, uint32_t* pin_k);
 
 /* Buffer-index launcher (abnn_launch_traversal): the last pass's pre-gated
  * and refractory-surviving events {g1, g2} from its workspace (synchronises

@@ -2,7 +2,8 @@
 # VGPRs / scratch / LDS of every kernel of the HIP library (the stream loop
 # must not spill: a spilled in-flight load register drains every load).
 cd "$(dirname "$0")/.." || exit 1
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -c abnn_amd/csrc/kernels.hip \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
+    -mllvm -structurizecfg-skip-uniform-regions -c abnn_amd/csrc/kernels.hip \
     -o /tmp/abnn_k.o -Rpass-analysis=kernel-resource-usage 2>&1 |
   python3 -c '
 import re, sys

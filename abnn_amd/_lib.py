@@ -171,6 +171,35 @@ class SelectConfig(C.Structure):
     ]
 
 
+GRAPH_MAX_BLOCKS = 16
+GRAPH_KEY = 0xD1B54A32D192ED03
+TOPO_DENSE, TOPO_RANDOM, TOPO_RING = 0, 1, 2
+W_UNIFORM, W_BETA = 0, 1
+
+
+class GraphBlock(C.Structure):
+    """abnn_graph_block -- one block of a graph spec: count, the two populations, the topology and the weight law."""
+
+    _fields_ = [
+        ("count", C.c_uint64),
+        ("src_first", C.c_uint32), ("src_count", C.c_uint32),
+        ("dst_first", C.c_uint32), ("dst_count", C.c_uint32),
+        ("topology", C.c_uint32), ("k", C.c_uint32), ("p_rewire", C.c_float),
+        ("weight_law", C.c_uint32), ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("beta_a", C.c_uint32), ("beta_b", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class GraphSpec(C.Structure):
+    """abnn_graph_spec -- the seed and up to GRAPH_MAX_BLOCKS blocks laid end to end (entries past n_blocks zero)."""
+
+    _fields_ = [
+        ("seed", C.c_uint64), ("n_blocks", C.c_uint32), ("reserved", C.c_uint32),
+        ("blocks", GraphBlock * GRAPH_MAX_BLOCKS),
+    ]
+
+
 class SpikesConfig(C.Structure):
     """abnn_spikes_config -- the spike recorder's capacities, neuron range (count 0 = every neuron) and counts switch."""
 
@@ -252,6 +281,9 @@ SIGNATURES = [
     ("abnn_download_synapses", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_generate_synapses", C.c_int, [_VP, _U64]),
     ("abnn_checksum_synapses", C.c_int, [_VP, _PU64]),
+    ("abnn_graph_records", C.c_uint64, [C.POINTER(GraphSpec)]),
+    ("abnn_graph_fill_host", C.c_int, [C.POINTER(GraphSpec), _U64, _U64, _VP]),
+    ("abnn_build_graph", C.c_int, [_VP, C.POINTER(GraphSpec)]),
     ("abnn_census_words", C.c_uint64, [C.POINTER(CensusConfig)]),
     ("abnn_census_enqueue", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _VP]),
     ("abnn_census", C.c_int, [_VP, C.POINTER(CensusConfig), _VP, _U64]),
@@ -334,7 +366,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_spikes_start", "abnn_spikes_stop", "abnn_spikes_clear", "abnn_spikes_get_info",
                    "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts",
                    "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree",
-                   "abnn_select_words", "abnn_select_enqueue", "abnn_select")
+                   "abnn_select_words", "abnn_select_enqueue", "abnn_select",
+                   "abnn_graph_records", "abnn_graph_fill_host", "abnn_build_graph")
 
 _lib = None
 

@@ -157,6 +157,13 @@ class Brain:
         """build_random_graph recipe (brain-engine.cpp:31-53), generated on the GPU."""
         call("abnn_generate_synapses", self._h, seed)
 
+    def build_graph(self, spec: _lib.GraphSpec) -> None:
+        """Fill this handle's records from a graph spec on the GPU
+        (abnn_build_graph; abnn_amd.graph builds specs): local
+        record k becomes global record syn_offset + k of the spec.  The neuron
+        state and the scalars are untouched."""
+        call("abnn_build_graph", self._h, C.byref(spec))
+
     def checksum(self) -> int:
         v = C.c_uint64()
         call("abnn_checksum_synapses", self._h, C.byref(v))

@@ -19,6 +19,7 @@
 #include "census.h"
 #include "degree.h"
 #include "select.h"
+#include "graph.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -105,6 +106,8 @@ struct abnn_brain {
     uint64_t* degree_out = nullptr;  // abnn_degree's device result, grown to the largest one asked
     uint64_t degree_cap = 0;
     SelectScratch select;            // abnn_select_*: per-tile counts and offsets for syn_capacity (its first call)
+    uint32_t graph_blocks = 0;       // abnn_build_graph: the most workgroups of its launch (64 per CU; ABNN_GRAPH_BLOCKS)
+    bool graph_nt = false;           // ... with non-temporal stores (ABNN_GRAPH_NT=1)
     uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
@@ -991,6 +994,9 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     d.adapt_ranges = std::getenv("ABNN_STATIC_RANGES") ? 0u : 1u;
     b->select_blocks = 4u * (uint32_t)std::max(1, b->cus);  // 32 waves per CU, as the census
     if (const char* env = std::getenv("ABNN_SELECT_BLOCKS")) b->select_blocks = (uint32_t)std::max(1, std::atoi(env));
+    b->graph_blocks = 64u * (uint32_t)std::max(1, b->cus);  // measured: the finer grid evens the tail out
+    if (const char* env = std::getenv("ABNN_GRAPH_BLOCKS")) b->graph_blocks = (uint32_t)std::max(1, std::atoi(env));
+    if (const char* env = std::getenv("ABNN_GRAPH_NT")) b->graph_nt = std::atoi(env) != 0;
     if ((s = reset_ranges(b)) != ABNN_OK) return fail(s);
     *out = b;
     return ABNN_OK;
@@ -1119,6 +1125,47 @@ abnn_status abnn_checksum_synapses(abnn_brain* b, uint64_t* out)
     HIP_TRY(hipMemcpyAsync(out, b->u64_scratch, sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
     return ABNN_OK;
+}
+
+/* ---- graph builder (graph.hip) ------------------------------ */
+
+uint64_t abnn_graph_records(const abnn_graph_spec* spec) { return graph_records(spec); }
+
+namespace {
+const char* const kGraphInvalid =
+    "graph: n_blocks must be 1..16, reserved words and the blocks past n_blocks 0; per block count 1..2^59-1, "
+    "non-empty populations below 2^32, a known topology (k and p_rewire only with RING: one population, 1 <= k < n, "
+    "p_rewire in [0, 1]) and weight law (beta_a, beta_b only with BETA: >= 1, a + b - 1 <= 15), finite w_lo <= w_hi";
+}
+
+abnn_status abnn_graph_fill_host(const abnn_graph_spec* spec, uint64_t first, uint64_t n, abnn_synapse* out_host)
+{
+    REQUIRE(spec && (out_host || n == 0), "null argument");
+    const uint64_t total = graph_records(spec);
+    REQUIRE(total != 0, kGraphInvalid);
+    REQUIRE(first <= total && n <= total - first, "abnn_graph_fill_host: the range ends past abnn_graph_records(spec)");
+    graph_fill(graph_table(*spec), first, n, out_host);
+    return ABNN_OK;
+}
+
+abnn_status abnn_build_graph(abnn_brain* b, const abnn_graph_spec* spec)
+{
+    REQUIRE(b && spec, "null argument");
+    const uint64_t total = graph_records(spec);
+    REQUIRE(total != 0, kGraphInvalid);
+    REQUIRE(b->dims.syn_offset <= total && b->dims.n_syn <= total - b->dims.syn_offset,
+            "abnn_build_graph: syn_offset + n_syn exceeds abnn_graph_records(spec)");
+    for (uint32_t j = 0; j < spec->n_blocks; ++j) {
+        const abnn_graph_block& k = spec->blocks[j];
+        REQUIRE((uint64_t)k.src_first + k.src_count <= b->n_nrn && (uint64_t)k.dst_first + k.dst_count <= b->n_nrn,
+                "abnn_build_graph: a population ends above N_NRN");
+    }
+    ST_TRY(sync_all(b));
+    HIP_TRY(launch_build_graph(b->d.syn, b->dims.n_syn, b->dims.syn_offset, graph_table(*spec), b->graph_blocks,
+                               b->graph_nt, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    b->records_invalid = false;
+    return retally(b, 0, b->dims.n_syn);
 }
 
 /* ---- synapse census (census.hip) --------------------------- */

@@ -333,6 +333,19 @@ class ShardedBrain:
         self.global_events = int(t.item())
         self.brain.set_global_events(self.global_events)
 
+    def build_graph(self, spec) -> None:
+        """Brain.build_graph of this rank's slice [lo, hi) of the spec
+        (abnn_build_graph is shard-aware through syn_offset; no communication).
+        The spec's total must be the global record count."""
+        from . import graph as _graph
+
+        total = _graph.records(spec)
+        if total == 0:
+            raise ValueError("build_graph: invalid spec")
+        if total != self.n_syn_global:
+            raise ValueError(f"build_graph: the spec holds {total} records, the sharded graph {self.n_syn_global}")
+        self.brain.build_graph(spec)
+
     def census(self, bins: int, lo: float, hi: float, src=None, dst=None) -> dict:
         """Brain.census over every shard's records (collective: every rank
         calls it at the same point and gets the whole graph's result): the

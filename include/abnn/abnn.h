@@ -276,6 +276,92 @@ abnn_status abnn_generate_synapses(abnn_brain* b, uint64_t seed);
 /* Order-sensitive 64-bit checksum of the local synapse array (device-side). */
 abnn_status abnn_checksum_synapses(abnn_brain* b, uint64_t* out);
 
+/* ---- graph builder -------------------------------------------
+ * The reference's specification asks for more graphs than its code builds
+ * (README §6: "Generate connectivity (Erdős–Rényi or small-world)", "Initialize
+ * weights ~ Beta(2,8)").  A graph is described as up to ABNN_GRAPH_MAX_BLOCKS
+ * BLOCKS laid end to end in global record order: block j holds count_j records,
+ * and global record start_j + r (start_j = the sum of the earlier counts) is
+ * record r of block j.  A block names a source population [src_first, src_first
+ * + S), a target population [dst_first, dst_first + D), a topology and a weight
+ * law.  Every record is a closed-form function of (spec.seed, j, r): the result
+ * does not depend on the grid, a shard generates exactly its slice [syn_offset,
+ * syn_offset + n_syn), and a block's records depend on its number and the
+ * seed alone, not on the counts or contents of the blocks before it (abnn_amd/
+ * graph.py restates the rule in numpy).
+ * The draws.  X(c) = splitmix64_at(seed ^ (ABNN_GRAPH_KEY * (j + 1)), (r << 5)
+ * | c) for c < 32, in u64 arithmetic, where
+ *   splitmix64_at(s, k): z = s + (k + 1) * 0x9E3779B97F4A7C15;
+ *     z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) *
+ *     0x94D049BB133111EB; return z ^ z >> 31.
+ *   u(c) = (float)(X(c) >> 40) * 2^-24 (unit24: 24 bits, exact, in [0, 1)).
+ *   pick(c, n) = (uint32_t)(((X(c) >> 32) * n) >> 32).
+ * Topologies give (src, dst):
+ *   DENSE:  src = src_first + (r / D) % S,  dst = dst_first + r % D.
+ *   RANDOM: src = src_first + pick(0, S),   dst = dst_first + pick(1, D).
+ *   RING:   one population (src_first == dst_first, S == D == n) and 1 <= k < n.
+ *           i = (r / k) % n, q = r % k, o = (q >> 1) + 1; the lattice target is
+ *           t = (i + ((q & 1) ? n - o : o)) % n: i+1, i-1, i+2, i-2, ... -- k
+ *           distinct neighbours, none of them i.  If u(0) < p_rewire (one fp32
+ *           compare) the edge is rewired: t = (i + 1 + pick(1, n - 1)) % n,
+ *           uniform over the other n - 1 nodes, never a self-loop.
+ *           src = src_first + i, dst = src_first + t.
+ * Weight.  w = w_lo + v * (w_hi - w_lo) as three separate fp32 operations (the
+ * subtraction, the product, the addition; no fused multiply-add), with
+ *   UNIFORM: v = u(2);
+ *   BETA:    v = the beta_a-th smallest of u(2) ... u(2 + m - 1), m = beta_a +
+ *            beta_b - 1: exactly Beta(a, b) for integer parameters, by
+ *            comparisons alone (Beta(2,8): the second smallest of nine draws).
+ * pad = 0.  With a count above S * D (DENSE) or n * k (RING) the pattern
+ * repeats, with fresh weights.                                               */
+#define ABNN_GRAPH_MAX_BLOCKS 16
+#define ABNN_GRAPH_KEY 0xD1B54A32D192ED03ull
+#define ABNN_TOPO_DENSE  0u   /* all-to-all, row-major                                  */
+#define ABNN_TOPO_RANDOM 1u   /* src, dst uniform and independent (Erdős–Rényi G(n,M) with
+                                 replacement: multi-edges and self-loops allowed, as
+                                 brain-engine.cpp:46-47)                                 */
+#define ABNN_TOPO_RING   2u   /* directed Watts–Strogatz: ring lattice of out-degree k,
+                                 each edge rewired with probability p_rewire            */
+#define ABNN_W_UNIFORM 0u
+#define ABNN_W_BETA    1u     /* Beta(a, b), integer a, b: an order statistic of uniforms */
+typedef struct abnn_graph_block {        /* 64 bytes */
+    uint64_t count;                      /* 1 .. 2^59 - 1 */
+    uint32_t src_first, src_count;       /* S = src_count >= 1 */
+    uint32_t dst_first, dst_count;       /* D = dst_count >= 1 */
+    uint32_t topology, k;                /* k: RING only, else 0 */
+    float    p_rewire;                   /* RING only (0..1), else +0.0f */
+    uint32_t weight_law;
+    float    w_lo, w_hi;                 /* finite, w_lo <= w_hi */
+    uint32_t beta_a, beta_b;             /* BETA only: >= 1, a + b - 1 <= 15; else 0 */
+    uint32_t reserved[2];                /* 0 */
+} abnn_graph_block;
+typedef struct abnn_graph_spec {         /* 1040 bytes */
+    uint64_t seed;
+    uint32_t n_blocks, reserved;         /* 1 .. 16; 0 */
+    abnn_graph_block blocks[ABNN_GRAPH_MAX_BLOCKS];   /* entries past n_blocks all zero */
+} abnn_graph_spec;
+/* The sum of the counts, or 0 for an invalid spec (whatever can be checked
+ * without a handle): null; n_blocks outside 1..16; a reserved word that is not
+ * 0 or a non-zero byte in a block past n_blocks; a count of 0 or >= 2^59; S or
+ * D of 0, or first + count above 2^32; an unknown topology or weight law; k or
+ * p_rewire (any bits but +0.0f) set on a block that is not RING; a RING block
+ * with different populations, k == 0, k >= n, or p_rewire outside [0, 1] or
+ * NaN; beta_a or beta_b set on a block that is not BETA; a BETA block with a
+ * zero parameter or a + b - 1 > 15; a bound that is not finite, w_lo > w_hi.   */
+uint64_t    abnn_graph_records(const abnn_graph_spec* spec);
+/* The rule on the host, without a device or a handle: global records [first,
+ * first + n) of the spec into out_host.  ABNN_ERR_INVALID: a null spec (or a
+ * null out_host with n > 0), an invalid spec, first + n above its total.       */
+abnn_status abnn_graph_fill_host(const abnn_graph_spec* spec, uint64_t first, uint64_t n, abnn_synapse* out_host);
+/* Synchronous, as abnn_generate_synapses: waits for the device, fills the
+ * handle's local records k < n_syn with global record syn_offset + k of the
+ * spec, waits again; the records are valid afterwards and the pruning tally is
+ * recounted.  The neuron state and the scalars are untouched; nothing at or
+ * past n_syn is written.  ABNN_ERR_INVALID (the records stay as they were): a
+ * null argument, an invalid spec, syn_offset + n_syn > abnn_graph_records(spec),
+ * a population that ends above N_NRN.  n_syn == 0 is valid.                   */
+abnn_status abnn_build_graph(abnn_brain* b, const abnn_graph_spec* spec);
+
 /* ---- synapse census ----------------------------------------
  * One streaming pass over the handle's local records [0, n_syn): live and
  * tombstone counts and a histogram of the selected weights, without moving the

@@ -373,6 +373,12 @@ public:
         touch();
         check(abnn_generate_synapses(h_, seed), "abnn_generate_synapses");
     }
+    // Fill the records from a graph spec on the device (abnn_build_graph; the rule is in abnn.h).
+    void build_graph(const abnn_graph_spec& spec)
+    {
+        touch();
+        check(abnn_build_graph(h_, &spec), "abnn_build_graph");
+    }
     void set_auto_stimulus(uint64_t first, uint64_t count)
     {
         check(abnn_set_auto_stimulus(h_, first, count), "abnn_set_auto_stimulus");

@@ -171,6 +171,24 @@ class SelectConfig(C.Structure):
     ]
 
 
+HOPS_MAX = 1024
+HOPS_REVERSE, HOPS_WEIGHT = 1, 2
+HOPS_HEADER_WORDS = 8
+HOPS_UNREACHED = 0xFFFFFFFF
+HOPS_BEGIN = 0xFFFFFFFF
+
+
+class HopsConfig(C.Structure):
+    """abnn_hops_config -- the seed range, the hop limit, the flags and the weight bounds of a reachability search."""
+
+    _fields_ = [
+        ("seed_first", C.c_uint32), ("seed_count", C.c_uint32),
+        ("max_hops", C.c_uint32), ("flags", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 GRAPH_MAX_BLOCKS = 16
 GRAPH_KEY = 0xD1B54A32D192ED03
 TOPO_DENSE, TOPO_RANDOM, TOPO_RING = 0, 1, 2
@@ -293,6 +311,10 @@ SIGNATURES = [
     ("abnn_select_words", C.c_uint64, [C.POINTER(SelectConfig), _U64]),
     ("abnn_select_enqueue", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _VP]),
     ("abnn_select", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _U64]),
+    ("abnn_hops_words", C.c_uint64, [C.POINTER(HopsConfig), _U64]),
+    ("abnn_hops_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _VP]),
+    ("abnn_hops_step_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), C.c_uint32, _VP, _VP]),
+    ("abnn_hops", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _U64]),
     ("abnn_spikes_start", C.c_int, [_VP, C.POINTER(SpikesConfig)]),
     ("abnn_spikes_stop", C.c_int, [_VP]),
     ("abnn_spikes_clear", C.c_int, [_VP, C.c_int]),
@@ -367,7 +389,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_spikes_read_passes", "abnn_spikes_read_raster", "abnn_spikes_read_counts",
                    "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree",
                    "abnn_select_words", "abnn_select_enqueue", "abnn_select",
-                   "abnn_graph_records", "abnn_graph_fill_host", "abnn_build_graph")
+                   "abnn_graph_records", "abnn_graph_fill_host", "abnn_build_graph",
+                   "abnn_hops_words", "abnn_hops_enqueue", "abnn_hops_step_enqueue", "abnn_hops")
 
 _lib = None
 

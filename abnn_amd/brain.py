@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib
 from . import census as _census
 from . import degree as _degree
+from . import hops as _hops
 from . import select as _select
 from . import spikes as _spikes
 from ._lib import Dims, Params, Scalars, State, Stats, call
@@ -234,6 +235,34 @@ class Brain:
         synchronises after the handle's first select.  Plane entries at and
         past ``written`` are not written.  Decode with select.decode."""
         call("abnn_select_enqueue", self._h, C.byref(cfg), int(capacity), int(out_ptr), _stream_ptr(stream))
+
+    def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
+        """Reachability on the device (abnn_hops): the hop
+        distance of every neuron from the seed range ``seeds`` = (first,
+        count) over this handle's records, at most ``max_hops`` hops;
+        ``reverse`` follows dst -> src (who can reach the seeds), ``weights`` =
+        (w_lo, w_hi) follows only records with w_lo <= w < w_hi; the rule is
+        in abnn.h.  Returns records, neurons, reached, depth, complete,
+        ``levels`` (np.uint64) and ``dist`` (np.uint32, hops.UNREACHED = not
+        reached) (hops.decode)."""
+        cfg = _hops.config(seeds, max_hops, reverse, weights)
+        n_nrn = self.n_neuron()
+        words = int(self._lib.abnn_hops_words(C.byref(cfg), n_nrn))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_hops", self._h, C.byref(cfg), _ptr(out), words)  # an invalid config fails here
+        return _hops.decode(out, cfg, n_nrn)
+
+    def hops_enqueue(self, cfg: _lib.HopsConfig, out_ptr: int, stream=None) -> None:
+        """Enqueue a whole search into device memory at ``out_ptr``
+        (abnn_hops_words(cfg, N_NRN) u64) on ``stream``; nothing synchronises
+        after the handle's first search.  Decode with hops.decode."""
+        call("abnn_hops_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
+
+    def hops_step_enqueue(self, cfg: _lib.HopsConfig, step: int, out_ptr: int, stream=None) -> None:
+        """Enqueue one step (hops.BEGIN, or 0 .. max_hops) of a search in the
+        device memory at ``out_ptr``: the sharded caller's path, which merges
+        the ranks' planes (hops.merge_planes) between two steps."""
+        call("abnn_hops_step_enqueue", self._h, C.byref(cfg), int(step), int(out_ptr), _stream_ptr(stream))
 
     # ---- spike recorder (abnn_spikes_*, DESIGN.md §9) -------------------------------------------
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:

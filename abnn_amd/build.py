@@ -9,6 +9,7 @@
 * ``build_degree_test()`` : g++ -> tests/cpp/degree_test (the degree census's C++ mirrors)
 * ``build_select_test()`` : g++ -> tests/cpp/select_test (the synapse select's C++ mirrors)
 * ``build_graph_test()``  : g++ -> tests/cpp/graph_test (the graph builder's C++ mirror vs abnn_graph_fill_host)
+* ``build_hops_test()``   : g++ -> tests/cpp/hops_test (the reachability search's C++ mirrors vs a host BFS)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -25,10 +26,11 @@ CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
-               os.path.join(CSRC, "graph.hip")]
+               os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
+                          os.path.join(CSRC, "hops.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -51,6 +53,8 @@ SELECT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "select_test.cpp")
 SELECT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "select_test")
 GRAPH_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "graph_test.cpp")
 GRAPH_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "graph_test")
+HOPS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "hops_test.cpp")
+HOPS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "hops_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -260,6 +264,20 @@ def build_graph_test(force: bool = False) -> str | None:
     return GRAPH_TEST_BIN
 
 
+def build_hops_test(force: bool = False) -> str | None:
+    """Test program of the reachability search's C++ mirrors (Brain::hops,
+    HopsView vs a host BFS; the step path with a host-side minimum over two handles)."""
+    if not os.path.exists(HOPS_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [HOPS_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(HOPS_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", HOPS_TEST_BIN, HOPS_TEST_SRC, "-L", PKG, "-labnn_hip", "-ldl",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return HOPS_TEST_BIN
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -284,6 +302,7 @@ def build_all(force: bool = False) -> None:
     build_degree_test(force)
     build_select_test(force)
     build_graph_test(force)
+    build_hops_test(force)
     build_learn_bench(force)
 
 

@@ -20,6 +20,7 @@
 #include "degree.h"
 #include "select.h"
 #include "graph.h"
+#include "hops.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -106,6 +107,9 @@ struct abnn_brain {
     uint64_t* degree_out = nullptr;  // abnn_degree's device result, grown to the largest one asked
     uint64_t degree_cap = 0;
     SelectScratch select;            // abnn_select_*: per-tile counts and offsets for syn_capacity (its first call)
+    uint32_t* hops_bitmap = nullptr; // abnn_hops_*: the frontier bitmap, N_NRN bits (its first call)
+    uint64_t* hops_out = nullptr;    // abnn_hops's device result, grown to the largest one asked
+    uint64_t hops_cap = 0;
     uint32_t graph_blocks = 0;       // abnn_build_graph: the most workgroups of its launch (64 per CU; ABNN_GRAPH_BLOCKS)
     bool graph_nt = false;           // ... with non-temporal stores (ABNN_GRAPH_NT=1)
     uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
@@ -180,7 +184,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -1333,6 +1337,78 @@ abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t c
     }
     (void)hipFree(dev);
     HIP_TRY(e);
+    return ABNN_OK;
+}
+
+/* ---- reachability (hops.hip) --------------------------------- */
+
+uint64_t abnn_hops_words(const abnn_hops_config* cfg, uint64_t n_nrn) { return hops_words(cfg, n_nrn); }
+
+namespace {
+
+// The checks of a search on handle b, then its scratch (the first call
+// allocates it: that one may synchronise the device).
+abnn_status hops_check(abnn_brain* b, const abnn_hops_config* cfg)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(hops_config_ok(cfg, b->n_nrn),
+            "hops: seed_count >= 1 and the seed range inside N_NRN, max_hops in 1..1024, no unknown flags, reserved 0, "
+            "w_lo / w_hi +0 without WEIGHT, with it no NaN bound and w_lo < w_hi");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // no memset: every step writes every word of the bitmap before it reads it
+    if (!b->hops_bitmap)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->hops_bitmap), hops_bitmap_words(b->n_nrn) * sizeof(uint32_t)));
+    return ABNN_OK;
+}
+
+abnn_status hops_steps(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_dev, hipStream_t s)
+{
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_hops_step(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, ABNN_HOPS_BEGIN, out_dev, b->hops_bitmap,
+                             (uint32_t)b->cus, s));
+    for (uint32_t h = 0; h <= cfg->max_hops; ++h)
+        HIP_TRY(launch_hops_step(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, h, out_dev, b->hops_bitmap, (uint32_t)b->cus, s));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_hops_enqueue(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 7u) == 0, "hops: out_dev must be 8-byte aligned");
+    ST_TRY(hops_check(b, cfg));
+    return hops_steps(b, cfg, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_hops_step_enqueue(abnn_brain* b, const abnn_hops_config* cfg, uint32_t step, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 7u) == 0, "hops: out_dev must be 8-byte aligned");
+    ST_TRY(hops_check(b, cfg));
+    REQUIRE(step == ABNN_HOPS_BEGIN || step <= cfg->max_hops, "hops: a step is ABNN_HOPS_BEGIN or 0 .. max_hops");
+    HIP_TRY(launch_hops_step(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, step, out_dev, b->hops_bitmap, (uint32_t)b->cus,
+                             pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(hops_check(b, cfg));
+    REQUIRE(words == hops_words(cfg, b->n_nrn), "abnn_hops: words must equal abnn_hops_words(cfg, N_NRN)");
+    ST_TRY(sync_all(b));
+    if (words > b->hops_cap) {
+        if (b->hops_out) (void)hipFree(b->hops_out);
+        b->hops_out = nullptr;
+        b->hops_cap = 0;
+        ST_TRY(dalloc(&b->hops_out, words));
+        b->hops_cap = words;
+    }
+    ST_TRY(hops_steps(b, cfg, b->hops_out, b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->hops_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
     return ABNN_OK;
 }
 

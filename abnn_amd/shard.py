@@ -428,6 +428,43 @@ class ShardedBrain:
         out["records"], out["tombstones"] = int(t_sum[0].item()), int(t_sum[1].item())
         return out
 
+    def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
+        """Brain.hops over every shard's records (collective: every rank calls
+        it at the same point and gets the whole graph's result).  Every rank
+        holds some of the edges, so this drives the steps itself
+        (hops_step_enqueue) and, between two steps, replaces every rank's
+        plane with the element-wise minimum over the ranks: the comm has no
+        min reduction, so the plane goes through all_reduce_max as inverted
+        distances (H - d; unreached stays -1).  The merged planes are equal, so
+        every rank counts the same levels[h] and skips the dead steps at the
+        same point.  Word 0 (records) is summed over the ranks."""
+        from . import hops as _hops
+
+        torch, dev = self._torch, self.xchg.device
+        cfg = _hops.config(seeds, max_hops, reverse, weights)
+        n_nrn = self.brain.n_neuron()
+        words = _hops.n_words(cfg, n_nrn)
+        if not words:
+            raise ValueError("hops: invalid config")
+        H, at = int(cfg.max_hops), _hops.plane_offset(cfg)
+        out = torch.zeros(words, dtype=torch.int64, device=dev)
+        plane = out[at:].view(torch.int32)  # UNREACHED is -1; the pad entry of an odd N_NRN stays 0
+        stream = torch.cuda.current_stream(dev)
+        self.brain.hops_step_enqueue(cfg, _hops.BEGIN, out.data_ptr(), stream)
+        for h in range(H):
+            self.brain.hops_step_enqueue(cfg, h, out.data_ptr(), stream)
+            if int(out[_hops.HOPS_HEADER_WORDS + h].item()) == 0:
+                break  # the same on every rank: the steps up to H - 1 are dead
+            inv = torch.where(plane < 0, plane, H - plane)
+            self.comm.all_reduce_max(inv)
+            plane.copy_(torch.where(inv < 0, inv, H - inv))
+        self.brain.hops_step_enqueue(cfg, H, out.data_ptr(), stream)
+        records = torch.tensor([self.brain.n_syn()], dtype=torch.int64, device=dev)
+        self.comm.all_reduce_sum(records)
+        got = out.cpu().numpy().view(np.uint64)
+        got[0] = int(records.item())
+        return _hops.decode(got, cfg, n_nrn)
+
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
         """Brain.record_spikes on the local handle.  No collective: every
         rank's spike list is the merged global one, so any rank's recorder

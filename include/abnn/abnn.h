@@ -510,6 +510,83 @@ abnn_status abnn_select_enqueue(abnn_brain* b, const abnn_select_config* cfg, ui
  * copied, the rest of out_host is left untouched.                             */
 abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_host, uint64_t words);
 
+/* ---- reachability: hop distances from a seed set -------------
+ * A breadth-first search over the handle's local records [0, n_syn), on the
+ * device: the hop distance of every neuron from a seed set S = [seed_first,
+ * seed_first + seed_count), at most H = max_hops hops, without moving the
+ * records to the host.  One hop is one streaming pass over the records against
+ * a one-bit-per-neuron frontier map.
+ * Followed records.  Record k < n_syn is FOLLOWED when it is live (dst !=
+ * 0xFFFFFFFF), src < N_NRN and dst < N_NRN (records written through
+ * abnn_state_ptrs are not validated: nothing outside the planes is indexed) and,
+ * with ABNN_HOPS_WEIGHT, w >= w_lo && w < w_hi as single fp32 comparisons (NaN
+ * is never followed; the bounds rules are abnn_select's).  A followed record is
+ * the edge u -> v = src -> dst, with ABNN_HOPS_REVERSE dst -> src (who can reach
+ * the seeds).  Records at or past n_syn are never read.
+ * Result: 8 + (H + 1) + (N_NRN + 1) / 2 u64 words:
+ *   0 the handle's n_syn   1 N_NRN   2 reached = the sum of the levels
+ *   3 depth: the largest h with levels[h] > 0
+ *   4 complete: 1 iff levels[H] == 0 (the search ran out of frontier: every
+ *     reachable neuron is in the plane)                           5..7 zero
+ *   8 ...          levels[0..H], one word each: the neurons at distance h
+ *   8 + H + 1 ...  the distance plane: N_NRN little-endian u32 (an odd N_NRN is
+ *                  padded with one zero entry); entry n is the hop distance of
+ *                  neuron n from S: 0 for a seed, ABNN_HOPS_UNREACHED when it is
+ *                  not reached within H hops
+ * Steps.  abnn_hops_enqueue is exactly the steps BEGIN, 0, 1, ..., H in order:
+ *   BEGIN     zero the header and the levels; plane = 0 on S, UNREACHED elsewhere
+ *   h < H     if h > 0 and levels[h-1] == 0: nothing.  Else levels[h] = #{n :
+ *             plane[n] == h}; then plane[v] = min(plane[v], h + 1) for every
+ *             followed local record u -> v with plane[u] == h
+ *   H         levels[H] likewise (same early-out), then words 0..4
+ * The early-out is read on the device: the host enqueues every step and learns
+ * nothing in between; a dead step's kernels read one word and return.
+ * Distances are breadth-first levels, so the result depends on neither the
+ * grid nor the order nor the timing, and every word is an integer (abnn_amd/
+ * hops.py restates it in numpy).
+ * Shards.  A shard holds some of the edges.  A sharded caller runs the steps
+ * itself (abnn_hops_step_enqueue) and, between two steps, replaces every rank's
+ * plane with the element-wise minimum over the ranks; levels[h] is recounted
+ * from the plane at step h, so every rank ends with the same result: words 1..4
+ * describe the whole graph, word 0 is the rank's own n_syn.
+ * Scratch.  The frontier bitmap (N_NRN bits) stays with the handle: the FIRST
+ * hops call on a handle allocates it and may synchronise the device;
+ * abnn_brain_destroy frees it.  Two searches of one handle enqueued on
+ * different streams must be ordered by the caller.                            */
+#define ABNN_HOPS_MAX        1024u
+#define ABNN_HOPS_REVERSE    1u   /* follow dst -> src: who can reach the seeds */
+#define ABNN_HOPS_WEIGHT     2u   /* follow a record only if w_lo <= w && w < w_hi */
+#define ABNN_HOPS_HEADER_WORDS 8
+#define ABNN_HOPS_UNREACHED  0xFFFFFFFFu
+#define ABNN_HOPS_BEGIN      0xFFFFFFFFu   /* step value: initialise */
+typedef struct abnn_hops_config {   /* 32 bytes */
+    uint32_t seed_first, seed_count; /* the seed set [first, first+count), count >= 1 */
+    uint32_t max_hops;               /* H: 1 .. ABNN_HOPS_MAX */
+    uint32_t flags;
+    float    w_lo, w_hi;             /* as abnn_select_config: +0.0f unless WEIGHT */
+    uint32_t reserved[2];            /* 0 */
+} abnn_hops_config;
+/* The result's words for a brain of n_nrn neurons, or 0 for an invalid config:
+ * null, seed_count == 0, a seed range that ends above n_nrn, max_hops outside
+ * 1..ABNN_HOPS_MAX, unknown flag bits, a reserved word that is not 0, a
+ * non-zero w_lo or w_hi without WEIGHT, a NaN bound or w_lo >= w_hi with it,
+ * n_nrn == 0.                                                                 */
+uint64_t    abnn_hops_words(const abnn_hops_config* cfg, uint64_t n_nrn);
+/* Enqueue only: every step in order, in stream order on `stream`, into out_dev
+ * (DEVICE memory, 8-byte aligned, abnn_hops_words(cfg, N_NRN) u64); nothing
+ * synchronises after the handle's first hops call, so it can sit between
+ * passes.  ABNN_ERR_INVALID: a null argument, a config that is invalid for the
+ * handle's N_NRN, a handle whose records are invalid.  n_syn == 0 is valid and
+ * gives the seeds only.                                                       */
+abnn_status abnn_hops_enqueue(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_dev, void* stream);
+/* One step (ABNN_HOPS_BEGIN, or 0 .. max_hops) of the search in out_dev; also
+ * ABNN_ERR_INVALID for any other step value.  The caller runs BEGIN first and
+ * the steps in increasing order.                                              */
+abnn_status abnn_hops_step_enqueue(abnn_brain* b, const abnn_hops_config* cfg, uint32_t step, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_hops_words(cfg,
+ * N_NRN)).  Its device result stays with the handle until abnn_brain_destroy. */
+abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_host, uint64_t words);
+
 /* ---- spike recorder -----------------------------------------
  * A recorder attached to a handle.  While it is on, every pass the handle
  * completes (abnn_traverse, the passes inside abnn_engine_run, abnn_shard_commit

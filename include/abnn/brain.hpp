@@ -121,6 +121,26 @@ struct SelectView {
     }
 };
 
+// A view of a reachability result (abnn.h abnn_hops: the header, the levels
+// and the distance plane); it does not own the words.
+struct HopsView {
+    const uint64_t* words = nullptr;
+    uint32_t max_hops = 0;
+    HopsView(const uint64_t* w, const abnn_hops_config& cfg) : words(w), max_hops(cfg.max_hops) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t neurons() const { return words[1]; }
+    uint64_t reached() const { return words[2]; }
+    uint64_t depth() const { return words[3]; }
+    bool complete() const { return words[4] != 0; }
+    // levels()[h], h = 0 .. max_hops: the neurons at distance h
+    const uint64_t* levels() const { return words + ABNN_HOPS_HEADER_WORDS; }
+    // dist()[n], n < neurons(): the hop distance of neuron n, ABNN_HOPS_UNREACHED = not within max_hops
+    const uint32_t* dist() const
+    {
+        return reinterpret_cast<const uint32_t*>(words + ABNN_HOPS_HEADER_WORDS + max_hops + 1);
+    }
+};
+
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
@@ -450,6 +470,25 @@ public:
                         void* stream = nullptr) const
     {
         check(abnn_select_enqueue(h_, &cfg, capacity, out_dev, stream), "abnn_select_enqueue");
+    }
+    // Reachability on the device (abnn_hops; the rule is in abnn.h): the
+    // result's words, to be read through a HopsView.
+    std::vector<uint64_t> hops(const abnn_hops_config& cfg) const
+    {
+        const uint64_t words = abnn_hops_words(&cfg, n_neuron());
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_hops(h_, &cfg, w.data(), words), "abnn_hops");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_hops_words(&cfg, n_neuron()) u64.
+    void hops_enqueue(const abnn_hops_config& cfg, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_hops_enqueue(h_, &cfg, out_dev, stream), "abnn_hops_enqueue");
+    }
+    // One step (ABNN_HOPS_BEGIN, or 0 .. max_hops): the sharded caller's path.
+    void hops_step_enqueue(const abnn_hops_config& cfg, uint32_t step, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_hops_step_enqueue(h_, &cfg, step, out_dev, stream), "abnn_hops_step_enqueue");
     }
     // The spike recorder (abnn_spikes_*; the contract is in abnn.h): from
     // record_spikes on, every pass appends its spike list to device buffers.

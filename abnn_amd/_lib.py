@@ -171,6 +171,26 @@ class SelectConfig(C.Structure):
     ]
 
 
+EDIT_ANY, EDIT_WEIGHT, EDIT_CLAMP = 1, 2, 4
+EDIT_SET, EDIT_AFFINE, EDIT_SCALE_DST, EDIT_SCALE_SRC, EDIT_DRAW, EDIT_KILL = 0, 1, 2, 3, 4, 5
+EDIT_HEADER_WORDS = 8
+EDIT_KEY = 0x8CB92BA72F3D8DD7
+
+
+class EditConfig(C.Structure):
+    """abnn_edit_config -- a select's match fields, the op, its parameters, the clamp bounds and the DRAW seed."""
+
+    _fields_ = [
+        ("src_first", C.c_uint32), ("src_count", C.c_uint32),
+        ("dst_first", C.c_uint32), ("dst_count", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("flags", C.c_uint32), ("op", C.c_uint32),
+        ("a", C.c_float), ("b", C.c_float), ("c_lo", C.c_float), ("c_hi", C.c_float),
+        ("seed", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 HOPS_MAX = 1024
 HOPS_REVERSE, HOPS_WEIGHT = 1, 2
 HOPS_HEADER_WORDS = 8
@@ -311,6 +331,12 @@ SIGNATURES = [
     ("abnn_select_words", C.c_uint64, [C.POINTER(SelectConfig), _U64]),
     ("abnn_select_enqueue", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _VP]),
     ("abnn_select", C.c_int, [_VP, C.POINTER(SelectConfig), _U64, _VP, _U64]),
+    ("abnn_edit_words", C.c_uint64, [C.POINTER(EditConfig)]),
+    ("abnn_edit_enqueue", C.c_int, [_VP, C.POINTER(EditConfig), _VP, _VP, _VP]),
+    ("abnn_edit", C.c_int, [_VP, C.POINTER(EditConfig), _VP, _U64, _VP]),
+    ("abnn_edit_host", C.c_int, [C.POINTER(EditConfig), _U64, _U64, _VP, _U64, _VP, _VP]),
+    ("abnn_edit_factors_enqueue", C.c_int, [_VP, _VP, _U64, _F, _F, _F, _VP, _VP]),
+    ("abnn_edit_factors_host", C.c_int, [_VP, _U64, _F, _F, _F, _VP]),
     ("abnn_hops_words", C.c_uint64, [C.POINTER(HopsConfig), _U64]),
     ("abnn_hops_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _VP]),
     ("abnn_hops_step_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), C.c_uint32, _VP, _VP]),
@@ -390,7 +416,9 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_degree_words", "abnn_degree_enqueue", "abnn_degree",
                    "abnn_select_words", "abnn_select_enqueue", "abnn_select",
                    "abnn_graph_records", "abnn_graph_fill_host", "abnn_build_graph",
-                   "abnn_hops_words", "abnn_hops_enqueue", "abnn_hops_step_enqueue", "abnn_hops")
+                   "abnn_hops_words", "abnn_hops_enqueue", "abnn_hops_step_enqueue", "abnn_hops",
+                   "abnn_edit_words", "abnn_edit_enqueue", "abnn_edit", "abnn_edit_host",
+                   "abnn_edit_factors_enqueue", "abnn_edit_factors_host")
 
 _lib = None
 

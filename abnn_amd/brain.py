@@ -17,6 +17,7 @@ import numpy as np
 from . import _lib
 from . import census as _census
 from . import degree as _degree
+from . import edit as _edit
 from . import hops as _hops
 from . import select as _select
 from . import spikes as _spikes
@@ -235,6 +236,74 @@ class Brain:
         synchronises after the handle's first select.  Plane entries at and
         past ``written`` are not written.  Decode with select.decode."""
         call("abnn_select_enqueue", self._h, C.byref(cfg), int(capacity), int(out_ptr), _stream_ptr(stream))
+
+    def edit(self, op, *, src=None, dst=None, weights=None, any: bool = False, a: float = 0.0, b: float = 0.0,
+             clamp=None, seed: int = 0, plane=None) -> dict:
+        """Synapse edit on the device (abnn_edit): this handle's
+        records that match (the select's ``src`` / ``dst`` / ``weights`` /
+        ``any``) get a new weight by ``op`` (edit.OPS: set b; affine w * a + b;
+        scale_dst / scale_src w * plane[key - first]; draw uniform in [a, b]
+        from ``seed``; kill: the pruning tombstone), then ``clamp`` = (c_lo,
+        c_hi); the rule is in abnn.h.  ``plane``: the float32 factors of a
+        scale op, one per neuron of its range (every neuron when the range is
+        not set).  Returns records, tombstones, matched, changed, killed and
+        nonfinite (edit.decode)."""
+        cfg = _edit.config(op, src, dst, weights, any, a, b, clamp, seed)
+        out = np.zeros(_lib.EDIT_HEADER_WORDS, dtype=np.uint64)
+        if plane is not None:
+            plane = np.ascontiguousarray(plane, dtype=np.float32)
+        call("abnn_edit", self._h, C.byref(cfg), None if plane is None else _ptr(plane),
+             0 if plane is None else plane.shape[0], _ptr(out))  # an invalid config fails here
+        return _edit.decode(out)
+
+    def edit_enqueue(self, cfg: _lib.EditConfig, plane_ptr: Optional[int], out_ptr: int, stream=None) -> None:
+        """Enqueue an edit on ``stream``: the header into device memory at
+        ``out_ptr`` (8 u64), a scale op's factors from device memory at
+        ``plane_ptr`` (None otherwise); nothing synchronises.  Decode with
+        edit.decode."""
+        call("abnn_edit_enqueue", self._h, C.byref(cfg), int(plane_ptr) if plane_ptr else None, int(out_ptr),
+             _stream_ptr(stream))
+
+    def edit_factors_enqueue(self, strength_ptr: int, count: int, target: float, f_lo: float, f_hi: float,
+                             plane_ptr: int, stream=None) -> None:
+        """Enqueue the factors of synaptic scaling on ``stream``: ``count``
+        int64 fixed-point strength words in device memory at ``strength_ptr``
+        (a degree census's in_w / out_w plane) into float32 factors at
+        ``plane_ptr``: target / strength, clamped to [f_lo, f_hi], 1 where the
+        strength is not positive (edit.factors restates it)."""
+        call("abnn_edit_factors_enqueue", self._h, int(strength_ptr), int(count), float(target), float(f_lo),
+             float(f_hi), int(plane_ptr), _stream_ptr(stream))
+
+    def scale_inputs(self, target: float, neurons=None, limits=(0.5, 2.0)) -> dict:
+        """Homeostatic synaptic scaling on the device: every incoming weight
+        of each neuron of ``neurons`` = (first, count) (None: every neuron) is
+        multiplied by the neuron's factor target / (its summed input), clamped
+        to ``limits`` -- the degree census's in_w plane, the factors and the
+        scale_dst edit enqueued on one stream, one synchronise at the end.
+        Returns the edit's header and ``factors`` (np.float32, one per neuron)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n_nrn = self.n_neuron()
+        dcfg = _degree.config(neurons, ("in_w",))
+        words = _degree.n_words(dcfg, n_nrn)
+        if not words:
+            raise ValueError("scale_inputs: invalid neuron range")
+        m = words - _lib.DEGREE_HEADER_WORDS
+        ecfg = _edit.config("scale_dst", dst=None if neurons is None else (int(neurons[0]), int(neurons[1])))
+        with torch.cuda.device(dev):
+            deg = torch.zeros(words, dtype=torch.int64, device=dev)
+            plane = torch.zeros(m, dtype=torch.float32, device=dev)
+            head = torch.zeros(_lib.EDIT_HEADER_WORDS, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            self.degrees_enqueue(dcfg, deg.data_ptr(), stream)
+            self.edit_factors_enqueue(deg.data_ptr() + 8 * _lib.DEGREE_HEADER_WORDS, m, target, limits[0], limits[1],
+                                      plane.data_ptr(), stream)
+            self.edit_enqueue(ecfg, plane.data_ptr(), head.data_ptr(), stream)
+            stream.synchronize()
+        out = _edit.decode(head.cpu().numpy().view(np.uint64))
+        out["factors"] = plane.cpu().numpy()
+        return out
 
     def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
         """Reachability on the device (abnn_hops): the hop

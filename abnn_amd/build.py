@@ -10,6 +10,8 @@
 * ``build_select_test()`` : g++ -> tests/cpp/select_test (the synapse select's C++ mirrors)
 * ``build_graph_test()``  : g++ -> tests/cpp/graph_test (the graph builder's C++ mirror vs abnn_graph_fill_host)
 * ``build_hops_test()``   : g++ -> tests/cpp/hops_test (the reachability search's C++ mirrors vs a host BFS)
+* ``build_edit_test()``   : g++ -> tests/cpp/edit_test (the synapse edit's C++ mirror vs abnn_edit_host)
+* ``build_edit_host_test()`` : g++ -fsanitize -> tests/cpp/edit_host_test (the edit's host rule alone, CPU only)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -26,11 +28,11 @@ CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
-               os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip")]
+               os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
-                          os.path.join(CSRC, "hops.h"),
+                          os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -55,6 +57,10 @@ GRAPH_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "graph_test.cpp")
 GRAPH_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "graph_test")
 HOPS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "hops_test.cpp")
 HOPS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "hops_test")
+EDIT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "edit_test.cpp")
+EDIT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "edit_test")
+EDIT_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "edit_host_test.cpp")
+EDIT_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "edit_host_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -278,6 +284,34 @@ def build_hops_test(force: bool = False) -> str | None:
     return HOPS_TEST_BIN
 
 
+def build_edit_test(force: bool = False) -> str | None:
+    """Test program of the synapse edit's C++ mirror (Brain::edit, EditView
+    against abnn_edit_host on the generated graph)."""
+    if not os.path.exists(EDIT_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [EDIT_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(EDIT_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", EDIT_TEST_BIN, EDIT_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return EDIT_TEST_BIN
+
+
+def build_edit_host_test(force: bool = False, out: str | None = None) -> str | None:
+    """The stand-alone program over the synapse edit's host rule (csrc/edit.h
+    alone: no HIP, no library), with the address and undefined-behaviour
+    sanitizers: a CPU program, run by tests/test_edit_abi.py."""
+    if not os.path.exists(EDIT_HOST_TEST_SRC):
+        return None
+    target = out or EDIT_HOST_TEST_BIN
+    deps = [EDIT_HOST_TEST_SRC, os.path.join(CSRC, "edit.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+    if force or out or _stale(target, deps):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-o", target, EDIT_HOST_TEST_SRC])
+    return target
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -303,6 +337,7 @@ def build_all(force: bool = False) -> None:
     build_select_test(force)
     build_graph_test(force)
     build_hops_test(force)
+    build_edit_test(force)
     build_learn_bench(force)
 
 

@@ -19,6 +19,7 @@
 #include "census.h"
 #include "degree.h"
 #include "select.h"
+#include "edit.h"
 #include "graph.h"
 #include "hops.h"
 #include "engine.h"
@@ -113,6 +114,11 @@ struct abnn_brain {
     uint32_t graph_blocks = 0;       // abnn_build_graph: the most workgroups of its launch (64 per CU; ABNN_GRAPH_BLOCKS)
     bool graph_nt = false;           // ... with non-temporal stores (ABNN_GRAPH_NT=1)
     uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
+    uint32_t edit_blocks = 0;        // abnn_edit_*: the most workgroups of its launch (4 per CU; ABNN_EDIT_BLOCKS)
+    bool edit_nt = true;             // ... with non-temporal stores (ABNN_EDIT_NT=0: plain)
+    float* edit_plane = nullptr;     // abnn_edit's staged plane, grown to the largest one asked
+    uint64_t edit_plane_cap = 0;
+    uint64_t* edit_out = nullptr;    // abnn_edit's device result (allocated by its first call)
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
@@ -184,7 +190,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->edit_plane, b->edit_out, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -998,6 +1004,9 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     d.adapt_ranges = std::getenv("ABNN_STATIC_RANGES") ? 0u : 1u;
     b->select_blocks = 4u * (uint32_t)std::max(1, b->cus);  // 32 waves per CU, as the census
     if (const char* env = std::getenv("ABNN_SELECT_BLOCKS")) b->select_blocks = (uint32_t)std::max(1, std::atoi(env));
+    b->edit_blocks = 4u * (uint32_t)std::max(1, b->cus);  // as the select
+    if (const char* env = std::getenv("ABNN_EDIT_BLOCKS")) b->edit_blocks = (uint32_t)std::max(1, std::atoi(env));
+    if (const char* env = std::getenv("ABNN_EDIT_NT")) b->edit_nt = std::atoi(env) != 0;
     b->graph_blocks = 64u * (uint32_t)std::max(1, b->cus);  // measured: the finer grid evens the tail out
     if (const char* env = std::getenv("ABNN_GRAPH_BLOCKS")) b->graph_blocks = (uint32_t)std::max(1, std::atoi(env));
     if (const char* env = std::getenv("ABNN_GRAPH_NT")) b->graph_nt = std::atoi(env) != 0;
@@ -1337,6 +1346,99 @@ abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t c
     }
     (void)hipFree(dev);
     HIP_TRY(e);
+    return ABNN_OK;
+}
+
+/* ---- synapse edit (edit.hip) -------------------------------- */
+
+uint64_t abnn_edit_words(const abnn_edit_config* cfg) { return edit_words(cfg); }
+
+namespace {
+
+constexpr const char* kEditInvalid =
+    "edit: an unknown op or flag, reserved != 0, a parameter set that the op and flags do not read, a NaN in one that "
+    "is read, c_lo > c_hi, DRAW with a > b or a bound that is not finite, CLAMP with KILL, ANY with a SCALE op, or "
+    "what abnn_select_words refuses for the ranges and the weight bounds";
+
+// The checks of an edit over a brain of n_nrn neurons that need no device.
+abnn_status edit_check(const abnn_edit_config* cfg, uint64_t n_nrn, bool has_plane)
+{
+    REQUIRE(edit_words(cfg) != 0, kEditInvalid);
+    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= n_nrn, "edit: src range ends above N_NRN");
+    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= n_nrn, "edit: dst range ends above N_NRN");
+    REQUIRE(n_nrn <= kMaxNeurons, "edit: N_NRN above the library's limit");
+    REQUIRE(edit_is_scale(cfg->op) == has_plane, "edit: a SCALE op needs a plane, every other op none");
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_edit_enqueue(abnn_brain* b, const abnn_edit_config* cfg, const float* plane_dev, uint64_t* out_dev,
+                              void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(edit_check(cfg, b->n_nrn, plane_dev != nullptr));
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_edit(b->d.syn, b->dims.n_syn, edit_rule(*cfg, b->n_nrn, b->dims.syn_offset), plane_dev, b->d.dead,
+                        out_dev, b->edit_blocks, b->edit_nt, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_edit(abnn_brain* b, const abnn_edit_config* cfg, const float* plane_host, uint64_t plane_count,
+                      uint64_t out_host[ABNN_EDIT_HEADER_WORDS])
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(edit_check(cfg, b->n_nrn, plane_host != nullptr));
+    REQUIRE(plane_count == edit_plane_count(*cfg, b->n_nrn),
+            "abnn_edit: plane_count must equal the neurons of the SCALE op's range (N_NRN when it is not set), 0 otherwise");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    ST_TRY(sync_all(b));
+    if (!b->edit_out) ST_TRY(dalloc(&b->edit_out, ABNN_EDIT_HEADER_WORDS));
+    if (plane_count > b->edit_plane_cap) {
+        if (b->edit_plane) (void)hipFree(b->edit_plane);
+        b->edit_plane = nullptr;
+        b->edit_plane_cap = 0;
+        ST_TRY(dalloc(&b->edit_plane, plane_count));
+        b->edit_plane_cap = plane_count;
+    }
+    if (plane_count)
+        HIP_TRY(hipMemcpyAsync(b->edit_plane, plane_host, plane_count * sizeof(float), hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(launch_edit(b->d.syn, b->dims.n_syn, edit_rule(*cfg, b->n_nrn, b->dims.syn_offset),
+                        plane_count ? b->edit_plane : nullptr, b->d.dead, b->edit_out, b->edit_blocks, b->edit_nt,
+                        b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->edit_out, ABNN_EDIT_HEADER_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost,
+                           b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+abnn_status abnn_edit_host(const abnn_edit_config* cfg, uint64_t n_nrn, uint64_t syn_offset, abnn_synapse* records,
+                           uint64_t n, const float* plane, uint64_t out[ABNN_EDIT_HEADER_WORDS])
+{
+    REQUIRE(cfg && out && (records || n == 0), "null argument");
+    ST_TRY(edit_check(cfg, n_nrn, plane != nullptr));
+    edit_host(*cfg, n_nrn, syn_offset, records, n, plane, out);
+    return ABNN_OK;
+}
+
+abnn_status abnn_edit_factors_enqueue(abnn_brain* b, const uint64_t* strength_dev, uint64_t count, float target,
+                                      float f_lo, float f_hi, float* plane_dev, void* stream)
+{
+    REQUIRE(b && ((strength_dev && plane_dev) || count == 0), "null argument");
+    REQUIRE(edit_factors_ok(target, f_lo, f_hi), "edit factors: target > 0 finite and 0 < f_lo <= f_hi finite");
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(launch_edit_factors(strength_dev, count, target, f_lo, f_hi, plane_dev, b->edit_blocks, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, float target, float f_lo, float f_hi,
+                                   float* plane)
+{
+    REQUIRE((strength && plane) || count == 0, "null argument");
+    REQUIRE(edit_factors_ok(target, f_lo, f_hi), "edit factors: target > 0 finite and 0 < f_lo <= f_hi finite");
+    edit_factors_host(strength, count, target, f_lo, f_hi, plane);
     return ABNN_OK;
 }
 

@@ -428,6 +428,33 @@ class ShardedBrain:
         out["records"], out["tombstones"] = int(t_sum[0].item()), int(t_sum[1].item())
         return out
 
+    def edit(self, op, **kw) -> dict:
+        """Brain.edit over every shard's records (collective: every rank calls
+        it at the same point with the same arguments -- a scale op's ``plane``
+        included -- and edits its own shard; a draw gives every record what
+        the unsharded brain would give it).  The headers are summed
+        (all_reduce_sum): every rank gets the whole graph's."""
+        from . import edit as _edit
+
+        local = self.brain.edit(op, **kw)
+        t = self._torch.tensor([local[k] for k in _edit.KEYS], dtype=self._torch.int64, device=self.xchg.device)
+        self.comm.all_reduce_sum(t)
+        return dict(zip(_edit.KEYS, (int(v) for v in t.cpu().tolist())))
+
+    def scale_inputs(self, target: float, neurons=None, limits=(0.5, 2.0)) -> dict:
+        """Brain.scale_inputs over every shard's records (collective): a
+        neuron's inputs lie on every rank, so the factors come from the merged
+        in_w plane of the whole graph (:meth:`degrees`), the same on every
+        rank, and each rank scales its own records.  Returns the summed header
+        and ``factors``."""
+        from . import edit as _edit
+
+        deg = self.degrees(neurons, ("in_w",))
+        f = _edit.factors(deg["in_w"], target, limits[0], limits[1])
+        out = self.edit("scale_dst", dst=None if neurons is None else (int(neurons[0]), int(neurons[1])), plane=f)
+        out["factors"] = f
+        return out
+
     def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
         """Brain.hops over every shard's records (collective: every rank calls
         it at the same point and gets the whole graph's result).  Every rank

@@ -510,6 +510,107 @@ abnn_status abnn_select_enqueue(abnn_brain* b, const abnn_select_config* cfg, ui
  * copied, the rest of out_host is left untouched.                             */
 abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t capacity, uint64_t* out_host, uint64_t words);
 
+/* ---- synapse edit --------------------------------------------
+ * One streaming read-modify-write pass over the handle's local records [0,
+ * n_syn), on the device: lesion a population, re-draw a projection's weights,
+ * clamp or rescale a weight band, scale each neuron's inputs -- without moving
+ * the records to the host.  Records at or past n_syn are never read or written.
+ * A record MATCHES by abnn_select's rule, bit for bit (the tombstone never
+ * matches; S / D are the u32 range tests; ABNN_EDIT_ANY / ABNN_EDIT_WEIGHT have
+ * the values and the meaning of ABNN_SELECT_ANY / ABNN_SELECT_WEIGHT; NaN never
+ * matches a weight interval).  A matched record with weight w gets the value v,
+ * every operation a single IEEE fp32 operation (no fused multiply-add):
+ *   ABNN_EDIT_SET        v = b
+ *   ABNN_EDIT_AFFINE     t = w * a;  v = t + b
+ *   ABNN_EDIT_SCALE_DST  v = w * plane[key - first], key = the record's dst
+ *   ABNN_EDIT_SCALE_SRC  ... key = the record's src.  (first, M) is the dst /
+ *                        src range of the config, or (0, N_NRN) when that range
+ *                        is not set; plane is M f32.  A matched record whose
+ *                        key lies outside the plane (no valid record has one)
+ *                        is left as it is.
+ *   ABNN_EDIT_DRAW       d = b - a;  t = u * d;  v = a + t  (three operations,
+ *                        as abnn_graph_block's weight), u = unit24(
+ *                        splitmix64_at(seed ^ ABNN_EDIT_KEY, syn_offset + the
+ *                        local index)), the graph builder's functions: a shard
+ *                        draws what the unsharded brain draws.
+ *   ABNN_EDIT_KILL       the record becomes the pruning tombstone {src = dst =
+ *                        0xFFFFFFFF, w unchanged, 0}.
+ * With ABNN_EDIT_CLAMP (any op but KILL) two comparisons follow, so a NaN stays
+ * a NaN:  if (v < c_lo) v = c_lo;  if (v > c_hi) v = c_hi;
+ * The bits of v replace the bits of w; a v that is a NaN is stored as the quiet
+ * NaN 0x7FC00000 (IEEE leaves a NaN's sign and payload to the platform; so the
+ * host rule and the device agree on inf * 0 too).  A record is CHANGED when the stored
+ * bits differ from the old ones (-0.0 and +0.0 differ); only changed records
+ * are written.  KILL changes every record it matches.
+ * Result: ABNN_EDIT_HEADER_WORDS u64 words, all integers (the result depends on
+ * neither the grid nor the timing; abnn_amd/edit.py restates the rule in numpy):
+ *   0 records scanned (= n_syn)   1 tombstones among them before the edit
+ *   2 matched   3 changed   4 killed
+ *   5 matched records whose stored v is NaN or +-inf (non-zero: the edit
+ *     poisoned the traversal; KILL stores no v: 0)     6, 7 zero
+ * KILL's bookkeeping is the pruning path's: the tombstone src code in the src
+ * streams, the kills added to the structural update's tally (compact_every >
+ * 0), n_syn unchanged -- the next structural update removes the tombstones as
+ * it removes pruned ones; with compact_every == 0 they stay (a saved pruned
+ * brain).  abnn_stats.pruned is a pass statistic and is not touched.         */
+#define ABNN_EDIT_ANY     1u   /* = ABNN_SELECT_ANY */
+#define ABNN_EDIT_WEIGHT  2u   /* = ABNN_SELECT_WEIGHT */
+#define ABNN_EDIT_CLAMP   4u   /* clamp v to [c_lo, c_hi] after the op */
+#define ABNN_EDIT_SET       0u
+#define ABNN_EDIT_AFFINE    1u
+#define ABNN_EDIT_SCALE_DST 2u
+#define ABNN_EDIT_SCALE_SRC 3u
+#define ABNN_EDIT_DRAW      4u
+#define ABNN_EDIT_KILL      5u
+#define ABNN_EDIT_HEADER_WORDS 8
+#define ABNN_EDIT_KEY 0x8CB92BA72F3D8DD7ull
+typedef struct abnn_edit_config {        /* 64 bytes */
+    uint32_t src_first, src_count;       /* as abnn_select_config */
+    uint32_t dst_first, dst_count;
+    float    w_lo, w_hi;                 /* read only with ABNN_EDIT_WEIGHT; else both +0.0f */
+    uint32_t flags, op;
+    float    a, b;                       /* SET reads b; AFFINE and DRAW read a and b */
+    float    c_lo, c_hi;                 /* read only with ABNN_EDIT_CLAMP */
+    uint64_t seed;                       /* DRAW only */
+    uint32_t reserved[2];                /* 0 */
+} abnn_edit_config;
+/* ABNN_EDIT_HEADER_WORDS, or 0 for a config that can be refused without a
+ * handle: everything abnn_select_words refuses for the shared fields; an unknown
+ * op or flag bit; reserved != 0; any of a, b, c_lo, c_hi, seed that the op and
+ * the flags do not read and whose bits are not all zero; a NaN in a parameter
+ * that is read; c_lo > c_hi; DRAW with a > b or a bound that is not finite;
+ * CLAMP with KILL; ANY with a SCALE op (the key could fall outside the plane). */
+uint64_t    abnn_edit_words(const abnn_edit_config* cfg);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, 8 u64) and edits the
+ * records in stream order on `stream`; no synchronise and no workgroup waits for
+ * another, so it can sit between passes and between abnn_engine_run calls.
+ * plane_dev: the M f32 factors of a SCALE op in DEVICE memory, NULL otherwise.
+ * A shard handle edits its own records.  ABNN_ERR_INVALID: a null argument, an
+ * invalid config, a range that ends above N_NRN, plane_dev null with a SCALE op
+ * or non-null without one, a handle whose records are invalid.  n_syn == 0 is
+ * valid.                                                                       */
+abnn_status abnn_edit_enqueue(abnn_brain* b, const abnn_edit_config* cfg, const float* plane_dev, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: plane_host (plane_count == M f32; NULL and 0 without
+ * a SCALE op) is staged in scratch the handle owns (freed by abnn_brain_destroy). */
+abnn_status abnn_edit(abnn_brain* b, const abnn_edit_config* cfg, const float* plane_host, uint64_t plane_count, uint64_t out_host[8]);
+/* The rule on the host, without a device or a handle, on n interchange records
+ * in place (local record k has global index syn_offset + k; plane: M f32 for a
+ * SCALE op, else NULL).  ABNN_ERR_INVALID as abnn_edit_enqueue, for a brain of
+ * n_nrn neurons.                                                               */
+abnn_status abnn_edit_host(const abnn_edit_config* cfg, uint64_t n_nrn, uint64_t syn_offset, abnn_synapse* records, uint64_t n, const float* plane, uint64_t out[8]);
+/* Factors from a degree-census strength plane (the int64 fixed-point words of
+ * ABNN_DEG_IN_W / ABNN_DEG_OUT_W), `count` of them:
+ *   S = (float)(int64_t)word * 2^-24   (one conversion, round to nearest even,
+ *                                       then one exact product)
+ *   f = S > 0 ? target / S : 1.0f      (one correctly rounded fp32 division)
+ *   if (f < f_lo) f = f_lo;  if (f > f_hi) f = f_hi;
+ * target > 0 finite and 0 < f_lo <= f_hi finite, else ABNN_ERR_INVALID.  With
+ * it abnn_degree_enqueue -> abnn_edit_factors_enqueue -> abnn_edit_enqueue(
+ * SCALE_DST) is synaptic scaling with nothing returning to the host.  Enqueue
+ * only, on `stream`; strength_dev and plane_dev are DEVICE memory.            */
+abnn_status abnn_edit_factors_enqueue(abnn_brain* b, const uint64_t* strength_dev, uint64_t count, float target, float f_lo, float f_hi, float* plane_dev, void* stream);
+abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, float target, float f_lo, float f_hi, float* plane);
+
 /* ---- reachability: hop distances from a seed set -------------
  * A breadth-first search over the handle's local records [0, n_syn), on the
  * device: the hop distance of every neuron from a seed set S = [seed_first,

@@ -121,6 +121,19 @@ struct SelectView {
     }
 };
 
+// A view of an edit result (abnn.h abnn_edit: ABNN_EDIT_HEADER_WORDS words);
+// it does not own the words.
+struct EditView {
+    const uint64_t* words = nullptr;
+    explicit EditView(const uint64_t* w) : words(w) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }  // before the edit
+    uint64_t matched() const { return words[2]; }
+    uint64_t changed() const { return words[3]; }
+    uint64_t killed() const { return words[4]; }
+    uint64_t nonfinite() const { return words[5]; }  // non-zero: the edit stored a NaN or an inf
+};
+
 // A view of a reachability result (abnn.h abnn_hops: the header, the levels
 // and the distance plane); it does not own the words.
 struct HopsView {
@@ -470,6 +483,29 @@ public:
                         void* stream = nullptr) const
     {
         check(abnn_select_enqueue(h_, &cfg, capacity, out_dev, stream), "abnn_select_enqueue");
+    }
+    // Synapse edit on the device (abnn_edit; the rule is in abnn.h): the
+    // matching records get a new weight or become tombstones; the result's 8
+    // words, to be read through an EditView.  plane: the factors of a SCALE op
+    // (one per neuron of its range), empty otherwise.
+    std::vector<uint64_t> edit(const abnn_edit_config& cfg, const std::vector<float>& plane = {})
+    {
+        std::vector<uint64_t> w(ABNN_EDIT_HEADER_WORDS);
+        check(abnn_edit(h_, &cfg, plane.empty() ? nullptr : plane.data(), plane.size(), w.data()), "abnn_edit");
+        return w;
+    }
+    // Enqueue only: plane_dev (a SCALE op's factors, else null) and out_dev (8 u64) are device memory.
+    void edit_enqueue(const abnn_edit_config& cfg, const float* plane_dev, uint64_t* out_dev, void* stream = nullptr)
+    {
+        check(abnn_edit_enqueue(h_, &cfg, plane_dev, out_dev, stream), "abnn_edit_enqueue");
+    }
+    // Enqueue only: `count` strength words of a degree census (device memory) into factors target / strength
+    // clamped to [f_lo, f_hi] at plane_dev.
+    void edit_factors_enqueue(const uint64_t* strength_dev, uint64_t count, float target, float f_lo, float f_hi,
+                              float* plane_dev, void* stream = nullptr) const
+    {
+        check(abnn_edit_factors_enqueue(h_, strength_dev, count, target, f_lo, f_hi, plane_dev, stream),
+              "abnn_edit_factors_enqueue");
     }
     // Reachability on the device (abnn_hops; the rule is in abnn.h): the
     // result's words, to be read through a HopsView.

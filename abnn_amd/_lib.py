@@ -191,6 +191,28 @@ class EditConfig(C.Structure):
     ]
 
 
+SNAP_RECORDS, SNAP_STATE = 1, 2
+DIFF_MAX_BINS = 4096
+DIFF_HEADER_WORDS = 24
+
+
+class DiffConfig(C.Structure):
+    """abnn_diff_config -- the bins over d = w_now - w_then and the src / dst ranges of a snapshot diff (count 0 = any)."""
+
+    _fields_ = [
+        ("lo", C.c_float), ("hi", C.c_float), ("bins", C.c_uint32),
+        ("src_first", C.c_uint32), ("src_count", C.c_uint32),
+        ("dst_first", C.c_uint32), ("dst_count", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+class SnapshotInfo(C.Structure):
+    """abnn_snapshot_info -- a snapshot's host view: captures, n_syn and the mirrors at the last capture, its bytes."""
+
+    _fields_ = [("captures", C.c_uint64), ("n_syn", C.c_uint64), ("scalars", Scalars), ("bytes", C.c_uint64)]
+
+
 HOPS_MAX = 1024
 HOPS_REVERSE, HOPS_WEIGHT = 1, 2
 HOPS_HEADER_WORDS = 8
@@ -337,6 +359,15 @@ SIGNATURES = [
     ("abnn_edit_host", C.c_int, [C.POINTER(EditConfig), _U64, _U64, _VP, _U64, _VP, _VP]),
     ("abnn_edit_factors_enqueue", C.c_int, [_VP, _VP, _U64, _F, _F, _F, _VP, _VP]),
     ("abnn_edit_factors_host", C.c_int, [_VP, _U64, _F, _F, _F, _VP]),
+    ("abnn_snapshot_create", C.c_int, [_VP, C.POINTER(_VP)]),
+    ("abnn_snapshot_destroy", C.c_int, [_VP]),
+    ("abnn_snapshot_get_info", C.c_int, [_VP, C.POINTER(SnapshotInfo)]),
+    ("abnn_snapshot_capture_enqueue", C.c_int, [_VP, _VP, _VP]),
+    ("abnn_snapshot_restore", C.c_int, [_VP, _VP, _U32]),
+    ("abnn_snapshot_diff_words", C.c_uint64, [C.POINTER(DiffConfig)]),
+    ("abnn_snapshot_diff_enqueue", C.c_int, [_VP, _VP, _VP, C.POINTER(DiffConfig), _VP, _VP]),
+    ("abnn_snapshot_diff", C.c_int, [_VP, _VP, _VP, C.POINTER(DiffConfig), _VP, _U64]),
+    ("abnn_snapshot_diff_host", C.c_int, [C.POINTER(DiffConfig), _U64, _VP, _U64, _VP, _U64, _VP]),
     ("abnn_hops_words", C.c_uint64, [C.POINTER(HopsConfig), _U64]),
     ("abnn_hops_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _VP]),
     ("abnn_hops_step_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), C.c_uint32, _VP, _VP]),
@@ -418,7 +449,10 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_graph_records", "abnn_graph_fill_host", "abnn_build_graph",
                    "abnn_hops_words", "abnn_hops_enqueue", "abnn_hops_step_enqueue", "abnn_hops",
                    "abnn_edit_words", "abnn_edit_enqueue", "abnn_edit", "abnn_edit_host",
-                   "abnn_edit_factors_enqueue", "abnn_edit_factors_host")
+                   "abnn_edit_factors_enqueue", "abnn_edit_factors_host",
+                   "abnn_snapshot_create", "abnn_snapshot_destroy", "abnn_snapshot_get_info",
+                   "abnn_snapshot_capture_enqueue", "abnn_snapshot_restore", "abnn_snapshot_diff_words",
+                   "abnn_snapshot_diff_enqueue", "abnn_snapshot_diff", "abnn_snapshot_diff_host")
 
 _lib = None
 

@@ -305,6 +305,19 @@ class Brain:
         out["factors"] = plane.cpu().numpy()
         return out
 
+    def snapshot(self, stream=None):
+        """A device-side snapshot of this brain as it is now
+        (abnn_snapshot_*): create, capture on ``stream`` and
+        synchronise.  Returns a :class:`abnn_amd.snapshot.Snapshot`: restore()
+        rolls the brain back to it, diff() says what changed since, capture()
+        takes it again.  Close it before the brain."""
+        from .snapshot import Snapshot
+
+        snap = Snapshot(self)
+        snap.capture(stream)
+        self.synchronize(stream)
+        return snap
+
     def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
         """Reachability on the device (abnn_hops): the hop
         distance of every neuron from the seed range ``seeds`` = (first,

@@ -12,6 +12,8 @@
 * ``build_hops_test()``   : g++ -> tests/cpp/hops_test (the reachability search's C++ mirrors vs a host BFS)
 * ``build_edit_test()``   : g++ -> tests/cpp/edit_test (the synapse edit's C++ mirror vs abnn_edit_host)
 * ``build_edit_host_test()`` : g++ -fsanitize -> tests/cpp/edit_host_test (the edit's host rule alone, CPU only)
+* ``build_snapshot_test()``   : g++ -> tests/cpp/snapshot_test (the snapshots' C++ mirror vs abnn_snapshot_diff_host)
+* ``build_snapshot_host_test()`` : g++ -fsanitize -> tests/cpp/snapshot_host_test (the diff's host rule alone, CPU only)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -28,11 +30,12 @@ CSRC = os.path.join(PKG, "csrc")
 HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip"), os.path.join(CSRC, "raw.hip"),
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
-               os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip")]
+               os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
+               os.path.join(CSRC, "snapshot.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
-                          os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"),
+                          os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -61,6 +64,10 @@ EDIT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "edit_test.cpp")
 EDIT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "edit_test")
 EDIT_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "edit_host_test.cpp")
 EDIT_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "edit_host_test")
+SNAPSHOT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "snapshot_test.cpp")
+SNAPSHOT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "snapshot_test")
+SNAPSHOT_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "snapshot_host_test.cpp")
+SNAPSHOT_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "snapshot_host_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -312,6 +319,34 @@ def build_edit_host_test(force: bool = False, out: str | None = None) -> str | N
     return target
 
 
+def build_snapshot_test(force: bool = False) -> str | None:
+    """Test program of the snapshots' C++ mirror (Brain::snapshot / restore /
+    diff, DiffView against abnn_snapshot_diff_host on the generated graph)."""
+    if not os.path.exists(SNAPSHOT_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [SNAPSHOT_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(SNAPSHOT_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", SNAPSHOT_TEST_BIN, SNAPSHOT_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return SNAPSHOT_TEST_BIN
+
+
+def build_snapshot_host_test(force: bool = False, out: str | None = None) -> str | None:
+    """The stand-alone program over the snapshot diff's host rule
+    (csrc/snapshot.h alone: no HIP, no library), with the address and
+    undefined-behaviour sanitizers: a CPU program, run by tests/test_snapshot_abi.py."""
+    if not os.path.exists(SNAPSHOT_HOST_TEST_SRC):
+        return None
+    target = out or SNAPSHOT_HOST_TEST_BIN
+    deps = [SNAPSHOT_HOST_TEST_SRC, os.path.join(CSRC, "snapshot.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+    if force or out or _stale(target, deps):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-o", target, SNAPSHOT_HOST_TEST_SRC])
+    return target
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -338,6 +373,7 @@ def build_all(force: bool = False) -> None:
     build_graph_test(force)
     build_hops_test(force)
     build_edit_test(force)
+    build_snapshot_test(force)
     build_learn_bench(force)
 
 

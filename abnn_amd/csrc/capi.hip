@@ -20,6 +20,7 @@
 #include "degree.h"
 #include "select.h"
 #include "edit.h"
+#include "snapshot.h"
 #include "graph.h"
 #include "hops.h"
 #include "engine.h"
@@ -119,6 +120,7 @@ struct abnn_brain {
     float* edit_plane = nullptr;     // abnn_edit's staged plane, grown to the largest one asked
     uint64_t edit_plane_cap = 0;
     uint64_t* edit_out = nullptr;    // abnn_edit's device result (allocated by its first call)
+    uint64_t* diff_out = nullptr;    // abnn_snapshot_diff's device result (allocated by its first call)
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
@@ -190,7 +192,7 @@ void free_all(abnn_brain* b)
                     b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->edit_plane, b->edit_out, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->edit_plane, b->edit_out, b->diff_out, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -423,6 +425,33 @@ abnn_status reset_ranges(abnn_brain* b)
     return ABNN_OK;
 }
 
+// The sweep partition after dims.n_syn changed (a structural update, a
+// snapshot restore): configure, then the ranges.  The device is idle.
+abnn_status repartition(abnn_brain* b)
+{
+    DeviceState& d = b->d;
+    const uint32_t old_iters = d.iters, old_ranges = d.n_ranges;
+    configure(b);
+    if (d.n_ranges == old_ranges && old_iters > 0) {
+        // the same ranges over (nearly) the same records: keep the adapted
+        // partition -- rescaled if the sweep's length changed -- and the
+        // measured costs, instead of restarting from a uniform partition
+        // (a uniform one costs ~3 passes at several times the pass time)
+        if (d.iters != old_iters) {
+            std::vector<uint32_t> rb(d.n_ranges + 1);
+            for (uint32_t* buf : {d.range_bounds, d.range_bounds_prev}) {
+                HIP_TRY(hipMemcpy(rb.data(), buf, rb.size() * 4, hipMemcpyDeviceToHost));
+                for (auto& v : rb) v = (uint32_t)((uint64_t)v * d.iters / old_iters);
+                rb[d.n_ranges] = d.iters;
+                HIP_TRY(hipMemcpy(buf, rb.data(), rb.size() * 4, hipMemcpyHostToDevice));
+            }
+        }
+        return ABNN_OK;
+    }
+    b->last_pass_fused = false;  // new ranges: the measured costs do not apply
+    return reset_ranges(b);
+}
+
 // README §5 structural update (contract in abnn.h): the tombstones' span
 // [a, z) closes up in order and the hole at its end takes the array's last D
 // records (or the tail shifts down), then the grown records are appended in
@@ -466,26 +495,7 @@ abnn_status structural_update(abnn_brain* b)
     }
     b->dims.n_syn = n - w[2] + w[4];
     b->structural_updates += 1;
-    const uint32_t old_iters = d.iters, old_ranges = d.n_ranges;
-    configure(b);
-    if (d.n_ranges == old_ranges && old_iters > 0) {
-        // the same ranges over (nearly) the same records: keep the adapted
-        // partition -- rescaled if the sweep's length changed -- and the
-        // measured costs, instead of restarting from a uniform partition
-        // (a uniform one costs ~3 passes at several times the pass time)
-        if (d.iters != old_iters) {
-            std::vector<uint32_t> rb(d.n_ranges + 1);
-            for (uint32_t* buf : {d.range_bounds, d.range_bounds_prev}) {
-                HIP_TRY(hipMemcpy(rb.data(), buf, rb.size() * 4, hipMemcpyDeviceToHost));
-                for (auto& v : rb) v = (uint32_t)((uint64_t)v * d.iters / old_iters);
-                rb[d.n_ranges] = d.iters;
-                HIP_TRY(hipMemcpy(buf, rb.data(), rb.size() * 4, hipMemcpyHostToDevice));
-            }
-        }
-        return ABNN_OK;
-    }
-    b->last_pass_fused = false;  // new ranges: the measured costs do not apply
-    return reset_ranges(b);
+    return repartition(b);
 }
 
 // A host write to lastFired (or a clock change) up to `stamp`: the recent-spike
@@ -1439,6 +1449,250 @@ abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, flo
     REQUIRE((strength && plane) || count == 0, "null argument");
     REQUIRE(edit_factors_ok(target, f_lo, f_hi), "edit factors: target > 0 finite and 0 < f_lo <= f_hi finite");
     edit_factors_host(strength, count, target, f_lo, f_hi, plane);
+    return ABNN_OK;
+}
+
+/* ---- device-side snapshots (snapshot.hip) -------------------- */
+
+// A copy of a handle's state in device memory, sized for its syn_capacity and
+// N_NRN, and the host mirrors as they were when the last capture was enqueued.
+struct abnn_snapshot {
+    abnn_brain* b = nullptr;
+    SynArrays syn{};                 // lo, hi, dw of [0, n_syn); no src32 (restore rebuilds the mirror)
+    uint64_t* last_fired = nullptr;  // [n_nrn]
+    uint64_t* last_visited = nullptr;
+    uint64_t* scalars = nullptr;     // the scalar block: {clock, reward | rbar, pass_index}
+    uint4* grown = nullptr;          // genesis on: [grown_slots]
+    uint64_t grown_slots = 0;
+    uint64_t captures = 0, n_syn = 0, bytes = 0;
+    uint64_t clock_host = 0, pass_host = 0, rng = 0, max_host_stamp = 0;
+};
+
+namespace {
+
+void snapshot_free(abnn_snapshot* s)
+{
+    if (!s) return;
+    if (s->b) (void)hipSetDevice(s->b->device);
+    void* ptrs[] = {s->syn.lo, s->syn.hi, s->syn.dw, s->last_fired, s->last_visited, s->scalars, s->grown};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    delete s;
+}
+
+abnn_status snapshot_alloc(abnn_snapshot* s)
+{
+    const abnn_brain* b = s->b;
+    const uint64_t cap = b->dims.syn_capacity + 2;  // whole 16-B pairs
+    ST_TRY(dalloc(&s->syn.lo, cap));
+    ST_TRY(dalloc(&s->syn.hi, cap));
+    ST_TRY(dalloc(&s->syn.dw, cap));
+    ST_TRY(dalloc(&s->last_fired, b->n_nrn));
+    ST_TRY(dalloc(&s->last_visited, b->n_nrn));
+    ST_TRY(dalloc(&s->scalars, 3));
+    if (b->d.grown) {
+        s->grown_slots = (uint64_t)b->params.compact_every * b->params.max_spikes;
+        ST_TRY(dalloc(&s->grown, s->grown_slots));
+    }
+    s->bytes = cap * 11 + b->n_nrn * 16 + 24 + s->grown_slots * 16;
+    return ABNN_OK;
+}
+
+constexpr const char* kDiffInvalid =
+    "snapshot diff: bins must be 1..4096, lo < hi both finite with a finite bins / (hi - lo), reserved 0";
+
+// The checks of a diff over a brain of n_nrn neurons that need no device; *scale for the launch.
+abnn_status diff_check(const abnn_diff_config* cfg, uint64_t n_nrn, float* scale)
+{
+    REQUIRE(diff_config_ok(cfg, scale), kDiffInvalid);
+    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= n_nrn, "snapshot diff: src range ends above N_NRN");
+    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= n_nrn, "snapshot diff: dst range ends above N_NRN");
+    return ABNN_OK;
+}
+
+// ... and of its two sides on handle b.
+abnn_status diff_sides_check(const abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now)
+{
+    REQUIRE(then->b == b && (!now || now->b == b), "snapshot diff: a snapshot of another brain");
+    REQUIRE(then->captures > 0 && (!now || now->captures > 0), "snapshot diff: nothing was captured yet");
+    REQUIRE(now || !b->records_invalid, kRecordsInvalid);
+    return ABNN_OK;
+}
+
+hipError_t diff_launch(abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now, const abnn_diff_config& cfg,
+                       float scale, uint64_t* out_dev, hipStream_t s)
+{
+    // the host knows the handle's n_syn: structural updates synchronise
+    return launch_diff(then->syn, then->n_syn, now ? now->syn : b->d.syn, now ? now->n_syn : b->dims.n_syn,
+                       diff_rule(cfg, scale), out_dev, (uint32_t)b->cus, s);
+}
+
+}  // namespace
+
+abnn_status abnn_snapshot_create(abnn_brain* b, abnn_snapshot** out)
+{
+    REQUIRE(b && out, "null argument");
+    *out = nullptr;
+    HIP_TRY(hipSetDevice(b->device));
+    abnn_snapshot* s = new (std::nothrow) abnn_snapshot();
+    if (!s) return ABNN_ERR_OOM;
+    s->b = b;
+    const abnn_status st = snapshot_alloc(s);
+    if (st != ABNN_OK) {
+        snapshot_free(s);
+        return st;
+    }
+    const hipError_t e = hipDeviceSynchronize();  // the buffers' zeros
+    if (e != hipSuccess) {
+        snapshot_free(s);  // nothing half made
+        set_err(std::string("abnn_snapshot_create: hipDeviceSynchronize: ") + hipGetErrorString(e));
+        return ABNN_ERR_HIP;
+    }
+    *out = s;
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_destroy(abnn_snapshot* s)
+{
+    if (!s) return ABNN_OK;
+    (void)hipSetDevice(s->b->device);
+    (void)hipDeviceSynchronize();  // an enqueued capture or diff may still use the buffers
+    snapshot_free(s);
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_get_info(const abnn_snapshot* s, abnn_snapshot_info* out)
+{
+    REQUIRE(s && out, "null argument");
+    std::memset(out, 0, sizeof(*out));
+    out->captures = s->captures;
+    out->n_syn = s->n_syn;
+    out->scalars.clock = s->clock_host;
+    out->scalars.pass_index = s->pass_host;
+    out->bytes = s->bytes;
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_capture_enqueue(abnn_brain* b, abnn_snapshot* s, void* stream)
+{
+    REQUIRE(b && s, "null argument");
+    REQUIRE(s->b == b, "abnn_snapshot_capture_enqueue: a snapshot of another brain");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    hipStream_t q = pick(b, stream);
+    const DeviceState& d = b->d;
+    // the host knows n_syn: structural updates synchronise
+    const uint64_t n = b->dims.n_syn;
+    if (n) {
+        HIP_TRY(hipMemcpyAsync(s->syn.lo, d.syn.lo, n * 2, hipMemcpyDeviceToDevice, q));
+        HIP_TRY(hipMemcpyAsync(s->syn.hi, d.syn.hi, n, hipMemcpyDeviceToDevice, q));
+        HIP_TRY(hipMemcpyAsync(s->syn.dw, d.syn.dw, n * 8, hipMemcpyDeviceToDevice, q));
+    }
+    HIP_TRY(hipMemcpyAsync(s->last_fired, d.last_fired, b->n_nrn * 8, hipMemcpyDeviceToDevice, q));
+    HIP_TRY(hipMemcpyAsync(s->last_visited, d.last_visited, b->n_nrn * 8, hipMemcpyDeviceToDevice, q));
+    HIP_TRY(hipMemcpyAsync(s->scalars, b->scalar_block, 24, hipMemcpyDeviceToDevice, q));
+    if (s->grown) HIP_TRY(hipMemcpyAsync(s->grown, d.grown, s->grown_slots * 16, hipMemcpyDeviceToDevice, q));
+    // the mirrors as they are now: the passes enqueued so far have advanced them
+    s->n_syn = n;
+    s->clock_host = b->clock_host;
+    s->pass_host = b->pass_host;
+    s->rng = b->rng;
+    s->max_host_stamp = b->max_host_stamp;
+    s->captures += 1;
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_restore(abnn_brain* b, const abnn_snapshot* s, uint32_t what)
+{
+    REQUIRE(b && s, "null argument");
+    REQUIRE(s->b == b, "abnn_snapshot_restore: a snapshot of another brain");
+    REQUIRE(what != 0 && !(what & ~(ABNN_SNAP_RECORDS | ABNN_SNAP_STATE)),
+            "abnn_snapshot_restore: what must be ABNN_SNAP_RECORDS, ABNN_SNAP_STATE or both");
+    REQUIRE(s->captures > 0, "abnn_snapshot_restore: nothing was captured yet");
+    REQUIRE(!b->pending_walk, "abnn_snapshot_restore: a sharded pass is half done (abnn_shard_apply)");
+    ST_TRY(sync_all(b));
+    DeviceState& d = b->d;
+    if (what & ABNN_SNAP_RECORDS) {
+        // [0, n) come back; what lies at and past n stays (as after a shrinking
+        // structural update: a pass masks the events past its last one)
+        const uint64_t n = s->n_syn;
+        if (n) {
+            HIP_TRY(hipMemcpyAsync(d.syn.lo, s->syn.lo, n * 2, hipMemcpyDeviceToDevice, b->stream));
+            HIP_TRY(hipMemcpyAsync(d.syn.hi, s->syn.hi, n, hipMemcpyDeviceToDevice, b->stream));
+            HIP_TRY(hipMemcpyAsync(d.syn.dw, s->syn.dw, n * 8, hipMemcpyDeviceToDevice, b->stream));
+            HIP_TRY(launch_src32_sync(d.syn, n, b->stream));
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        if (n != b->dims.n_syn) {
+            b->dims.n_syn = n;
+            ST_TRY(repartition(b));
+        }
+        if (d.dead) {  // no tally is left past the records: appended records land there
+            const uint64_t nb = (b->dims.syn_capacity + kCompactChunk - 1) / kCompactChunk;
+            HIP_TRY(hipMemset(d.dead, 0, nb * sizeof(uint32_t)));
+            ST_TRY(retally(b, 0, n));
+        }
+        b->records_invalid = false;  // a restore is a reload
+    }
+    if (what & ABNN_SNAP_STATE) {
+        HIP_TRY(hipMemcpyAsync(d.last_fired, s->last_fired, b->n_nrn * 8, hipMemcpyDeviceToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(d.last_visited, s->last_visited, b->n_nrn * 8, hipMemcpyDeviceToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->scalar_block, s->scalars, 24, hipMemcpyDeviceToDevice, b->stream));
+        if (s->grown) HIP_TRY(hipMemcpyAsync(d.grown, s->grown, s->grown_slots * 16, hipMemcpyDeviceToDevice, b->stream));
+        if (d.visit_mark) HIP_TRY(hipMemsetAsync(d.visit_mark, 0, b->n_nrn, b->stream));
+        HIP_TRY(hipDeviceSynchronize());
+        b->marks_dirty = false;
+        b->clock_host = s->clock_host;
+        b->pass_host = s->pass_host;
+        b->rng = s->rng;
+        // the bitmap is rebuilt from lastFired; every restored stamp is at most
+        // the larger of the captured clock and what the host had written by
+        // then, so the steady-state build resumes once the clock has passed it
+        // (the handle's own value may lie ahead of a clock that moved back)
+        state_written(b, 0);
+        b->max_host_stamp = std::max(s->max_host_stamp, s->clock_host);
+        b->last_pass = ~0ull;  // no pass since: abnn_get_budget answers max_spikes
+    }
+    return ABNN_OK;
+}
+
+uint64_t abnn_snapshot_diff_words(const abnn_diff_config* cfg) { return diff_words(cfg); }
+
+abnn_status abnn_snapshot_diff_enqueue(abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now,
+                                       const abnn_diff_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && then && cfg && out_dev, "null argument");
+    float scale = 0.0f;
+    ST_TRY(diff_check(cfg, b->n_nrn, &scale));
+    ST_TRY(diff_sides_check(b, then, now));
+    HIP_TRY(hipSetDevice(b->device));
+    HIP_TRY(diff_launch(b, then, now, *cfg, scale, out_dev, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_diff(abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now,
+                               const abnn_diff_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && then && cfg && out_host, "null argument");
+    float scale = 0.0f;
+    ST_TRY(diff_check(cfg, b->n_nrn, &scale));
+    ST_TRY(diff_sides_check(b, then, now));
+    REQUIRE(words == diff_words(cfg), "abnn_snapshot_diff: words must equal abnn_snapshot_diff_words(cfg)");
+    ST_TRY(sync_all(b));
+    if (!b->diff_out) ST_TRY(dalloc(&b->diff_out, ABNN_DIFF_HEADER_WORDS + ABNN_DIFF_MAX_BINS));
+    HIP_TRY(diff_launch(b, then, now, *cfg, scale, b->diff_out, b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->diff_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+abnn_status abnn_snapshot_diff_host(const abnn_diff_config* cfg, uint64_t n_nrn, const abnn_synapse* then,
+                                    uint64_t n_then, const abnn_synapse* now, uint64_t n_now, uint64_t* out)
+{
+    REQUIRE(cfg && out && (then || n_then == 0) && (now || n_now == 0), "null argument");
+    float scale = 0.0f;
+    ST_TRY(diff_check(cfg, n_nrn, &scale));
+    diff_host(*cfg, scale, then, n_then, now, n_now, out);
     return ABNN_OK;
 }
 

@@ -455,6 +455,40 @@ class ShardedBrain:
         out["factors"] = f
         return out
 
+    def snapshot(self):
+        """Brain.snapshot of this rank's shard (every rank keeps its own;
+        no communication): create, capture and synchronise."""
+        return self.brain.snapshot()
+
+    def restore(self, snap, what=("records", "state")) -> None:
+        """Snapshot.restore on every rank (collective: every rank calls it at
+        the same point with its own snapshot of the same moment); a records
+        restore changes the shards' record counts, so the visited events are
+        re-summed as after a structural update."""
+        snap.restore(what)
+        self._updates = self.brain.structural_updates()
+        parts = (what,) if isinstance(what, str) else tuple(what)
+        if "records" in parts:
+            self.refresh_global_events()
+
+    def diff(self, snap, bins: int, lo: float, hi: float, src=None, dst=None, now=None) -> dict:
+        """Snapshot.diff over every shard's records (collective: every rank
+        calls it at the same point with its own snapshots and gets the whole
+        graph's result): every word summed as int64 (all_reduce_sum; net wraps
+        as the device's sum does), the largest |d| by all_reduce_max."""
+        from . import snapshot as _snapshot
+
+        torch = self._torch
+        cfg = _snapshot.config(bins, lo, hi, src, dst)
+        local = _snapshot.to_words(snap.diff(bins, lo, hi, src, dst, now=now))
+        t_sum = torch.from_numpy(local.view(np.int64).copy()).to(self.xchg.device)
+        t_max = torch.tensor([int(local[22])], dtype=torch.int64, device=self.xchg.device)
+        self.comm.all_reduce_sum(t_sum)
+        self.comm.all_reduce_max(t_max)
+        words = t_sum.cpu().numpy().view(np.uint64).copy()
+        words[22] = int(t_max.item())
+        return _snapshot.decode(words, cfg)
+
     def hops(self, seeds, max_hops: int = 64, reverse: bool = False, weights=None) -> dict:
         """Brain.hops over every shard's records (collective: every rank calls
         it at the same point and gets the whole graph's result).  Every rank

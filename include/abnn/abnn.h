@@ -611,6 +611,122 @@ abnn_status abnn_edit_host(const abnn_edit_config* cfg, uint64_t n_nrn, uint64_t
 abnn_status abnn_edit_factors_enqueue(abnn_brain* b, const uint64_t* strength_dev, uint64_t count, float target, float f_lo, float f_hi, float* plane_dev, void* stream);
 abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, float target, float f_lo, float f_hi, float* plane);
 
+/* ---- device-side snapshots: capture, roll back, diff ----------
+ * A snapshot keeps a copy of a handle's state in device memory: the records
+ * [0, n_syn) (11 B each: the two src streams and {dst, w}), the two timestamp
+ * planes, the scalar block and, with synaptogenesis on, the grown records that
+ * wait for the next structural update.  Capture is device-to-device copies in
+ * stream order; restore puts the copy back and redoes the handle's bookkeeping;
+ * the diff is one streaming pass over two record arrays.  Nothing moves to the
+ * host.
+ *
+ * Restore (synchronous: it waits for the device, as a structural update does).
+ * ABNN_SNAP_RECORDS: the records and n_syn are the captured ones; the sweep is
+ * partitioned for the restored n_syn as after a structural update, the records
+ * at and past n_syn are whatever was there (nothing reads them: a pass masks
+ * the events past its last one, exactly as after a shrinking structural
+ * update), the tombstone tally is recounted, a random-mode handle's src mirror
+ * rebuilt, and a handle whose records were invalid (a failed structural
+ * update) is usable again: a restore is a reload.  A shard handle's caller
+ * re-sums global_events afterwards (abnn_set_global_events), as after a
+ * structural update.
+ * ABNN_SNAP_STATE: lastFired, lastVisited, clock, reward, rbar, pass_index, the
+ * abnn_inject_inputs RNG and the grown records are the captured ones; the clock
+ * may move back; a shard's visit marks are cleared; abnn_get_budget answers
+ * max_spikes, as before a first pass.
+ * With both: capture after any passes, run any passes and structural updates,
+ * restore, run P passes -- the records, lastFired, lastVisited and the scalars
+ * are bit for bit what the same P passes gave when run straight after the
+ * capture.
+ * Not restored: the cumulative counters (abnn_get_stats, abnn_renormalisations,
+ * abnn_structural_updates), the spike recorder (passes after a restore append
+ * as usual), and an abnn_engine's own driver state (its rates, filters,
+ * windows and teacher RNG go on from where they are).                          */
+typedef struct abnn_snapshot abnn_snapshot;
+#define ABNN_SNAP_RECORDS 1u   /* the records [0, n_syn) and n_syn itself */
+#define ABNN_SNAP_STATE   2u   /* lastFired, lastVisited, clock, reward, rbar, pass_index,
+                                  the inject_inputs RNG, the grown records waiting for the
+                                  next structural update */
+typedef struct abnn_snapshot_info {   /* host view, no synchronise */
+    uint64_t captures;        /* 0: nothing captured yet */
+    uint64_t n_syn;           /* the handle's n_syn at the last capture */
+    abnn_scalars scalars;     /* clock and pass_index from the host mirrors at capture;
+                                 reward and rbar are 0 here (they live on the device) */
+    uint64_t bytes;           /* device memory the snapshot holds */
+} abnn_snapshot_info;
+/* Allocates for the handle's syn_capacity and N_NRN on the handle's device (may
+ * synchronise).  ABNN_ERR_OOM leaves nothing allocated.  Destroy a snapshot
+ * before its brain.                                                            */
+abnn_status abnn_snapshot_create(abnn_brain* b, abnn_snapshot** out);
+abnn_status abnn_snapshot_destroy(abnn_snapshot* s);
+abnn_status abnn_snapshot_get_info(const abnn_snapshot* s, abnn_snapshot_info* out);
+/* Enqueue only: device-to-device copies in stream order on `stream`, and the
+ * host mirrors (n_syn, clock, pass_index, the RNG) as they are at the call --
+ * passes and abnn_engine_run advance those when they enqueue, so a capture sits
+ * between them without a synchronise.  A second capture overwrites the first.
+ * ABNN_ERR_INVALID: a null argument, a snapshot of another brain, a handle
+ * whose records are invalid.                                                   */
+abnn_status abnn_snapshot_capture_enqueue(abnn_brain* b, abnn_snapshot* s, void* stream);
+/* what: ABNN_SNAP_RECORDS | ABNN_SNAP_STATE, at least one.  ABNN_ERR_INVALID:
+ * what is 0 or has unknown bits, nothing was captured yet, the snapshot belongs
+ * to another brain, or a sharded pass is half done (between abnn_shard_gate and
+ * abnn_shard_apply).                                                           */
+abnn_status abnn_snapshot_restore(abnn_brain* b, const abnn_snapshot* s, uint32_t what);
+
+/* The diff of two record arrays, `then` (a snapshot) and `now` (another
+ * snapshot of the same brain, or NULL = the handle's records).  A = record k of
+ * then, B = record k of now, for k < c = min(n_then, n_now); a tombstone is
+ * dst == 0xFFFFFFFF; every comparison is one u32 or one IEEE fp32 operation.
+ * Classes, in this order: both tombstones -> dead_both; A live, B a tombstone
+ * -> killed; A a tombstone, B live -> revived; both live with a different src
+ * or dst -> rewired; otherwise paired.  A paired record is SELECTED when it
+ * passes both ranges (x - first < count; count 0 passes anything).  A selected
+ * record with equal weight bits is same, else changed; for a changed record
+ * d = w_B - w_A (one subtraction): d != d -> nan; d > 0 -> up; d < 0 -> down;
+ * otherwise zero (a +0 / -0 pair).  A changed record with a non-NaN d counts,
+ * by the census's rule on d: d < lo -> under; d >= hi -> over; otherwise bin
+ * min((uint32_t)((d - lo) * scale), bins - 1), scale = (float)bins / (hi - lo);
+ * and it raises the maximum of the bits of |d| taken as a u32 (+inf allowed).
+ * With q(w) = (int32_t)(w * 16777216.0f), a weight summable iff |w| < 128: a
+ * changed record with both weights summable adds q_B - q_A to net (int64
+ * modulo 2^64) and |q_B - q_A| to abs, any other changed record 1 to
+ * not_summable.
+ * Result: ABNN_DIFF_HEADER_WORDS + bins u64 words:
+ *    0 n_now   1 n_then   2 compared = c   3 born = n_now - c   4 gone = n_then - c
+ *    5 dead_both   6 killed   7 revived   8 rewired   9 paired
+ *   10 selected   11 same   12 changed   13 up   14 down   15 zero   16 nan
+ *   17 under   18 over   19 net   20 abs   21 not_summable
+ *   22 bits of the largest |d| in the low 32 bits (0 with none)   23 zero
+ *   24... the bins
+ * compared = 5+6+7+8+9; selected = same + changed; changed = up + down + zero +
+ * nan; up + down + zero = under + over + sum of the bins.  Every word is an
+ * integer sum or maximum: the result depends on neither the grid nor the order
+ * (abnn_amd/snapshot.py restates it in numpy).  Shards diff their own records;
+ * a merge adds every word except 22, which takes the maximum.                  */
+#define ABNN_DIFF_MAX_BINS 4096
+#define ABNN_DIFF_HEADER_WORDS 24
+typedef struct abnn_diff_config {      /* 32 bytes; the fields and checks of abnn_census_config */
+    float lo, hi; uint32_t bins;       /* bins over d = w_now - w_then, [lo, hi) */
+    uint32_t src_first, src_count, dst_first, dst_count;   /* count 0 = any */
+    uint32_t reserved;
+} abnn_diff_config;
+/* ABNN_DIFF_HEADER_WORDS + bins, or 0 for an invalid config (the refusals of
+ * abnn_census_words).                                                          */
+uint64_t abnn_snapshot_diff_words(const abnn_diff_config* cfg);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, abnn_snapshot_diff_words
+ * (cfg) u64) in stream order on `stream`.  ABNN_ERR_INVALID: a null b, then, cfg
+ * or out_dev, an invalid config, a range that ends above N_NRN, a snapshot with
+ * nothing captured or of another brain, now == NULL on a handle whose records
+ * are invalid.  n_syn == 0 on either side is valid.                            */
+abnn_status abnn_snapshot_diff_enqueue(abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now, const abnn_diff_config* cfg, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_snapshot_diff_words(cfg)).
+ * Its device result buffer belongs to the handle (as abnn_census's): the
+ * snapshots are only read.                                                     */
+abnn_status abnn_snapshot_diff(abnn_brain* b, const abnn_snapshot* then, const abnn_snapshot* now, const abnn_diff_config* cfg, uint64_t* out_host, uint64_t words);
+/* The rule on the host, without a device or a handle, over interchange records
+ * of a brain of n_nrn neurons; out holds abnn_snapshot_diff_words(cfg) u64.    */
+abnn_status abnn_snapshot_diff_host(const abnn_diff_config* cfg, uint64_t n_nrn, const abnn_synapse* then, uint64_t n_then, const abnn_synapse* now, uint64_t n_now, uint64_t* out);
+
 /* ---- reachability: hop distances from a seed set -------------
  * A breadth-first search over the handle's local records [0, n_syn), on the
  * device: the hop distance of every neuron from a seed set S = [seed_first,

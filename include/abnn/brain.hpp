@@ -154,6 +154,77 @@ struct HopsView {
     }
 };
 
+// A view of a snapshot diff result (abnn.h abnn_snapshot_diff: the header and
+// the bins over d = w_now - w_then); it does not own the words.
+struct DiffView {
+    const uint64_t* words = nullptr;
+    uint32_t n_bins = 0;
+    DiffView(const uint64_t* w, const abnn_diff_config& cfg) : words(w), n_bins(cfg.bins) {}
+    uint64_t n_now() const { return words[0]; }
+    uint64_t n_then() const { return words[1]; }
+    uint64_t compared() const { return words[2]; }
+    uint64_t born() const { return words[3]; }
+    uint64_t gone() const { return words[4]; }
+    uint64_t dead_both() const { return words[5]; }
+    uint64_t killed() const { return words[6]; }
+    uint64_t revived() const { return words[7]; }
+    uint64_t rewired() const { return words[8]; }
+    uint64_t paired() const { return words[9]; }
+    uint64_t selected() const { return words[10]; }
+    uint64_t same() const { return words[11]; }
+    uint64_t changed() const { return words[12]; }
+    uint64_t up() const { return words[13]; }
+    uint64_t down() const { return words[14]; }
+    uint64_t zero() const { return words[15]; }
+    uint64_t nan() const { return words[16]; }
+    uint64_t under() const { return words[17]; }
+    uint64_t over() const { return words[18]; }
+    int64_t net() const { return (int64_t)words[19]; }  // 2^-24 fixed point
+    uint64_t abs() const { return words[20]; }
+    uint64_t not_summable() const { return words[21]; }
+    float max_abs() const  // the largest |d|
+    {
+        const uint32_t u = (uint32_t)words[22];
+        float x;
+        std::memcpy(&x, &u, 4);
+        return x;
+    }
+    const uint64_t* bins() const { return words + ABNN_DIFF_HEADER_WORDS; }
+};
+
+class Brain;
+
+// A device-side snapshot of one Brain (abnn.h abnn_snapshot_*): made by
+// Brain::snapshot, destroyed before its Brain.
+class Snapshot {
+public:
+    Snapshot(Snapshot&& o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    Snapshot& operator=(Snapshot&& o) noexcept
+    {
+        if (this != &o) {
+            abnn_snapshot_destroy(h_);
+            h_ = o.h_;
+            o.h_ = nullptr;
+        }
+        return *this;
+    }
+    Snapshot(const Snapshot&) = delete;
+    Snapshot& operator=(const Snapshot&) = delete;
+    ~Snapshot() { abnn_snapshot_destroy(h_); }
+    abnn_snapshot_info info() const
+    {
+        abnn_snapshot_info i{};
+        check(abnn_snapshot_get_info(h_, &i), "abnn_snapshot_get_info");
+        return i;
+    }
+    abnn_snapshot* handle() const { return h_; }
+
+private:
+    friend class Brain;
+    explicit Snapshot(abnn_snapshot* h) : h_(h) {}
+    abnn_snapshot* h_ = nullptr;
+};
+
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
@@ -506,6 +577,46 @@ public:
     {
         check(abnn_edit_factors_enqueue(h_, strength_dev, count, target, f_lo, f_hi, plane_dev, stream),
               "abnn_edit_factors_enqueue");
+    }
+    // Device-side snapshots (abnn_snapshot_*; the contract is in abnn.h).
+    // snapshot(): create, capture and synchronise; capture(): enqueue only.
+    Snapshot snapshot(void* stream = nullptr)
+    {
+        flush_shared();
+        abnn_snapshot* s = nullptr;
+        check(abnn_snapshot_create(h_, &s), "abnn_snapshot_create");
+        Snapshot snap(s);
+        capture(snap, stream);
+        synchronize(stream);
+        return snap;
+    }
+    void capture(Snapshot& s, void* stream = nullptr)
+    {
+        flush_shared();
+        check(abnn_snapshot_capture_enqueue(h_, s.handle(), stream), "abnn_snapshot_capture_enqueue");
+    }
+    // Roll back to the snapshot (synchronous): what = ABNN_SNAP_RECORDS | ABNN_SNAP_STATE.
+    void restore(const Snapshot& s, uint32_t what = ABNN_SNAP_RECORDS | ABNN_SNAP_STATE)
+    {
+        touch();
+        check(abnn_snapshot_restore(h_, s.handle(), what), "abnn_snapshot_restore");
+    }
+    // What changed since `then`: against another snapshot, or (now == nullptr)
+    // this Brain's records; the result's words, to be read through a DiffView.
+    std::vector<uint64_t> diff(const Snapshot& then, const abnn_diff_config& cfg, const Snapshot* now = nullptr) const
+    {
+        const uint64_t words = abnn_snapshot_diff_words(&cfg);
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_snapshot_diff(h_, then.handle(), now ? now->handle() : nullptr, &cfg, w.data(), words),
+              "abnn_snapshot_diff");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_snapshot_diff_words(&cfg) u64.
+    void diff_enqueue(const Snapshot& then, const abnn_diff_config& cfg, uint64_t* out_dev, void* stream = nullptr,
+                      const Snapshot* now = nullptr) const
+    {
+        check(abnn_snapshot_diff_enqueue(h_, then.handle(), now ? now->handle() : nullptr, &cfg, out_dev, stream),
+              "abnn_snapshot_diff_enqueue");
     }
     // Reachability on the device (abnn_hops; the rule is in abnn.h): the
     // result's words, to be read through a HopsView.

@@ -13,11 +13,12 @@ this package is its Python host mirror:
 * :mod:`abnn_amd.hops` -- reachability: config, numpy reference, the merge of shard planes between steps;
 * :mod:`abnn_amd.graph` -- the graph builder: blocks, weight laws, spec, validator, numpy reference;
 * :mod:`abnn_amd.spikes` -- the spike recorder: config, pass dtype, numpy reference, raster split;
+* :mod:`abnn_amd.corr` -- spike correlograms: config, decode, numpy reference, merge of shard results;
 * :mod:`abnn_amd.shard` -- synapse-shard data parallelism over torch.distributed;
 * :mod:`abnn_amd.configs` -- the BASELINE.json workloads.
 """
-from . import census, degree, edit, graph, hops, select, snapshot, spikes
-from ._lib import (AbnnError, CensusConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, SelectConfig, SpikesConfig,
+from . import census, corr, degree, edit, graph, hops, select, snapshot, spikes
+from ._lib import (AbnnError, CensusConfig, CorrConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, SelectConfig, SpikesConfig,
                    default_params, device_count,
                    load as load_library)
 from .brain import SYN_DTYPE, Brain, visited_events
@@ -27,7 +28,7 @@ from .snapshot import Snapshot
 from .spikes import SPIKE_PASS_DTYPE
 
 __all__ = [
-    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
-    "SelectConfig", "Snapshot", "SpikesConfig", "Workload", "default_engine_config", "census", "default_params", "degree",
+    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "CorrConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
+    "SelectConfig", "Snapshot", "SpikesConfig", "Workload", "default_engine_config", "census", "corr", "default_params", "degree",
     "device_count", "edit", "graph", "hops", "load_library", "select", "snapshot", "spikes", "visited_events",
 ]

@@ -289,6 +289,25 @@ class SpikesInfo(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+CORR_MAX_LAG = 256
+CORR_MAX_PAIR_WORDS = 1 << 24
+CORR_POP, CORR_PAIRS, CORR_SYNAPSES = 0, 1, 2
+CORR_WEIGHT = 1
+CORR_HEADER_WORDS = 8
+
+
+class CorrConfig(C.Structure):
+    """abnn_corr_config -- the two populations, the row window, the largest lag, the mode and the weight bounds."""
+
+    _fields_ = [
+        ("a_first", C.c_uint32), ("a_count", C.c_uint32), ("b_first", C.c_uint32), ("b_count", C.c_uint32),
+        ("row_first", C.c_uint64), ("row_count", C.c_uint64),
+        ("max_lag", C.c_uint32), ("mode", C.c_uint32), ("flags", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
 LAYOUT_MAX_ARRAYS = 4
 
 
@@ -379,6 +398,11 @@ SIGNATURES = [
     ("abnn_spikes_read_passes", C.c_int, [_VP, _U64, _U64, _VP]),
     ("abnn_spikes_read_raster", C.c_int, [_VP, _U64, _U64, _VP]),
     ("abnn_spikes_read_counts", C.c_int, [_VP, _U64, _U64, _VP]),
+    ("abnn_spikes_load", C.c_int, [_VP, _VP, _U64, _VP, _U64]),
+    ("abnn_corr_words", C.c_uint64, [C.POINTER(CorrConfig)]),
+    ("abnn_corr_enqueue", C.c_int, [_VP, C.POINTER(CorrConfig), _VP, _VP]),
+    ("abnn_corr", C.c_int, [_VP, C.POINTER(CorrConfig), _VP, _U64]),
+    ("abnn_corr_host", C.c_int, [C.POINTER(CorrConfig), _U64, _VP, _U64, _VP, _U64, _VP, _U64, _VP]),
     ("abnn_get_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_set_last_fired", C.c_int, [_VP, _U64, _VP, _U64]),
     ("abnn_get_last_visited", C.c_int, [_VP, _U64, _VP, _U64]),
@@ -452,7 +476,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_edit_factors_enqueue", "abnn_edit_factors_host",
                    "abnn_snapshot_create", "abnn_snapshot_destroy", "abnn_snapshot_get_info",
                    "abnn_snapshot_capture_enqueue", "abnn_snapshot_restore", "abnn_snapshot_diff_words",
-                   "abnn_snapshot_diff_enqueue", "abnn_snapshot_diff", "abnn_snapshot_diff_host")
+                   "abnn_snapshot_diff_enqueue", "abnn_snapshot_diff", "abnn_snapshot_diff_host",
+                   "abnn_spikes_load", "abnn_corr_words", "abnn_corr_enqueue", "abnn_corr", "abnn_corr_host")
 
 _lib = None
 

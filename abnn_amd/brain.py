@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import census as _census
+from . import corr as _corr
 from . import degree as _degree
 from . import edit as _edit
 from . import hops as _hops
@@ -390,6 +391,37 @@ class Brain:
         """Free the recorder (synchronises)."""
         self._spk = None
         call("abnn_spikes_stop", self._h)
+
+    def load_spikes(self, passes: np.ndarray, raster: np.ndarray) -> None:
+        """Replace what the recorder holds with a host pass table
+        (spikes.SPIKE_PASS_DTYPE) and its raster (abnn_spikes_load;
+        synchronises): as after a clear followed by len(passes) recorded
+        passes.  Offsets, capacities and ids are checked first."""
+        passes = np.ascontiguousarray(passes, dtype=_spikes.SPIKE_PASS_DTYPE)
+        raster = np.ascontiguousarray(raster, dtype=np.uint32)
+        call("abnn_spikes_load", self._h, _ptr(passes) if len(passes) else None, len(passes),
+             _ptr(raster) if len(raster) else None, len(raster))
+
+    # ---- spike correlograms (abnn_corr_*, DESIGN.md §9) -----------------------------------------
+    def correlate(self, mode, a=None, b=None, max_lag: int = 16, rows=None, weights=None) -> dict:
+        """A correlogram of the recorded spikes on the device (abnn_corr,
+        DESIGN.md §9): ``mode`` "pop", "pairs" or "synapses"; ``a`` / ``b`` =
+        (first, count) of the pre / post population (None: every neuron),
+        lags -max_lag .. max_lag in table rows, ``rows`` = (first, count) of
+        the rows used (None: all), ``weights`` = (w_lo, w_hi) follows only
+        such records; the rule is in abnn.h.  Returns the header fields,
+        ``lags`` and ``plane`` (corr.decode)."""
+        cfg = _corr.config(mode, a, b, max_lag, rows, weights)
+        words = int(self._lib.abnn_corr_words(C.byref(cfg)))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_corr", self._h, C.byref(cfg), _ptr(out), words)  # an invalid config fails here
+        return _corr.decode(out, cfg)
+
+    def correlate_enqueue(self, cfg: _lib.CorrConfig, out_ptr: int, stream=None) -> None:
+        """Enqueue a correlogram into device memory at ``out_ptr``
+        (abnn_corr_words(cfg) u64) on ``stream``; nothing synchronises after
+        the handle's first one.  Decode with corr.decode."""
+        call("abnn_corr_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
 
     # ---- neuron state ---------------------------------------------------------------------------
     def last_fired(self, first: int = 0, n: Optional[int] = None) -> np.ndarray:

@@ -14,6 +14,8 @@
 * ``build_edit_host_test()`` : g++ -fsanitize -> tests/cpp/edit_host_test (the edit's host rule alone, CPU only)
 * ``build_snapshot_test()``   : g++ -> tests/cpp/snapshot_test (the snapshots' C++ mirror vs abnn_snapshot_diff_host)
 * ``build_snapshot_host_test()`` : g++ -fsanitize -> tests/cpp/snapshot_host_test (the diff's host rule alone, CPU only)
+* ``build_corr_test()``   : g++ -> tests/cpp/corr_test (the correlograms' C++ mirror vs abnn_corr_host)
+* ``build_corr_host_test()`` : g++ -fsanitize -> tests/cpp/corr_host_test (the correlograms' host rule alone, CPU only)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -31,11 +33,12 @@ HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip")
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
                os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
-               os.path.join(CSRC, "snapshot.hip")]
+               os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
+                          os.path.join(CSRC, "corr.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -68,6 +71,10 @@ SNAPSHOT_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "snapshot_test.cpp")
 SNAPSHOT_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "snapshot_test")
 SNAPSHOT_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "snapshot_host_test.cpp")
 SNAPSHOT_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "snapshot_host_test")
+CORR_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "corr_test.cpp")
+CORR_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "corr_test")
+CORR_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "corr_host_test.cpp")
+CORR_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "corr_host_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -347,6 +354,34 @@ def build_snapshot_host_test(force: bool = False, out: str | None = None) -> str
     return target
 
 
+def build_corr_test(force: bool = False) -> str | None:
+    """Test program of the correlograms' C++ mirror (Brain::load_spikes /
+    correlate, CorrView against abnn_corr_host on the generated graph)."""
+    if not os.path.exists(CORR_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [CORR_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(CORR_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", CORR_TEST_BIN, CORR_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return CORR_TEST_BIN
+
+
+def build_corr_host_test(force: bool = False, out: str | None = None) -> str | None:
+    """The stand-alone program over the correlograms' host rule (csrc/corr.h
+    alone: no HIP, no library), with the address and undefined-behaviour
+    sanitizers: a CPU program, run by tests/test_corr_abi.py."""
+    if not os.path.exists(CORR_HOST_TEST_SRC):
+        return None
+    target = out or CORR_HOST_TEST_BIN
+    deps = [CORR_HOST_TEST_SRC, os.path.join(CSRC, "corr.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+    if force or out or _stale(target, deps):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-o", target, CORR_HOST_TEST_SRC])
+    return target
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -374,6 +409,7 @@ def build_all(force: bool = False) -> None:
     build_hops_test(force)
     build_edit_test(force)
     build_snapshot_test(force)
+    build_corr_test(force)
     build_learn_bench(force)
 
 

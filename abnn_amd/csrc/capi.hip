@@ -26,6 +26,7 @@
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
+#include "corr.h"
 
 using namespace abnn;
 
@@ -122,6 +123,9 @@ struct abnn_brain {
     uint64_t* edit_out = nullptr;    // abnn_edit's device result (allocated by its first call)
     uint64_t* diff_out = nullptr;    // abnn_snapshot_diff's device result (allocated by its first call)
     SpikeRecorder spikes;            // abnn_spikes_*: on between start and stop (run_commit enqueues its launch)
+    CorrScratch corr;                // abnn_corr_*: the map, the planes, the row lists and the tallies (its first call)
+    uint64_t* corr_out = nullptr;    // abnn_corr's device result, grown to the largest one asked
+    uint64_t corr_cap = 0;
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
     uint64_t rot = 0;              // passes run by this handle: the bitmap buffers' rotation (never reset)
@@ -193,6 +197,7 @@ void free_all(abnn_brain* b)
                     b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
                     b->d.work,      b->idx_scratch,
                     b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->edit_plane, b->edit_out, b->diff_out, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
+                    b->corr.map, b->corr.cnt, b->corr.off, b->corr.cur, b->corr.rows, b->corr.tally, b->corr.cursor, b->corr_out,
                     b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
                     const_cast<uint32_t*>(b->d.dummy)};
     for (void* p : ptrs)
@@ -1875,6 +1880,126 @@ abnn_status abnn_spikes_read_counts(abnn_brain* b, uint64_t first_neuron, uint64
             "abnn_spikes_read_counts: neurons outside the selected range");
     ST_TRY(sync_all(b));
     if (n) HIP_TRY(hipMemcpy(out, r.counts + (first_neuron - r.first), n * sizeof(*out), hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+abnn_status abnn_spikes_load(abnn_brain* b, const abnn_spike_pass* passes, uint64_t n_passes, const uint32_t* raster,
+                             uint64_t n_raster)
+{
+    REQUIRE(b && (passes || n_passes == 0) && (raster || n_raster == 0), "null argument");
+    const SpikeRecorder& r = b->spikes;
+    REQUIRE(r.on, kNoRecorder);
+    REQUIRE(r.raster, "abnn_spikes_load: the recorder keeps no raster");
+    REQUIRE(n_passes <= r.cfg.pass_capacity && n_raster <= r.cfg.raster_capacity,
+            "abnn_spikes_load: more passes or spikes than the recorder holds");
+    uint64_t at = 0;
+    for (uint64_t k = 0; k < n_passes; ++k) {
+        REQUIRE(passes[k].offset == at && passes[k].count <= n_raster - at,
+                "abnn_spikes_load: the offsets must be 0, count_0, count_0 + count_1, ... inside the raster");
+        at += passes[k].count;
+    }
+    REQUIRE(at == n_raster, "abnn_spikes_load: the counts must sum to n_raster");
+    for (uint64_t i = 0; i < n_raster; ++i) {
+        REQUIRE(raster[i] < b->n_nrn, "abnn_spikes_load: an id at or above N_NRN");
+        REQUIRE(!r.cfg.count || raster[i] - r.cfg.first < r.cfg.count, "abnn_spikes_load: an id outside the recorder's range");
+    }
+    ST_TRY(sync_all(b));
+    if (n_passes) HIP_TRY(hipMemcpy(r.passes, passes, n_passes * sizeof(*passes), hipMemcpyHostToDevice));
+    if (n_raster) HIP_TRY(hipMemcpy(r.raster, raster, n_raster * sizeof(*raster), hipMemcpyHostToDevice));
+    const uint64_t tail[kSpikeWords - 3] = {n_passes, n_raster, 0, 0, 0};  // recorded, dropped, the flag
+    HIP_TRY(hipMemcpy(r.words + 3, tail, sizeof(tail), hipMemcpyHostToDevice));
+    HIP_TRY(hipDeviceSynchronize());
+    return ABNN_OK;
+}
+
+/* ---- spike correlograms (corr.hip) --------------------------- */
+
+uint64_t abnn_corr_words(const abnn_corr_config* cfg) { return corr_words(cfg); }
+
+namespace {
+
+constexpr const char* kCorrConfig =
+    "corr: mode POP / PAIRS / SYNAPSES, no unknown flags, max_lag <= 256, ranges inside N_NRN, PAIRS with both counts "
+    ">= 1 and at most 2^24 plane words, reserved 0, w_lo / w_hi +0 without WEIGHT, with it no NaN bound and w_lo < w_hi";
+
+// The checks of a correlogram on handle b, then its scratch (the first call,
+// and the first after the recorder was restarted larger, allocates it: that
+// one may synchronise the device).
+abnn_status corr_check(abnn_brain* b, const abnn_corr_config* cfg)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(corr_config_ok(cfg, nullptr) && corr_ranges_ok(*cfg, b->n_nrn), kCorrConfig);
+    REQUIRE(b->spikes.on, kNoRecorder);
+    REQUIRE(b->spikes.raster, "corr: the recorder keeps no raster");
+    REQUIRE(cfg->mode != ABNN_CORR_SYNAPSES || !b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    CorrScratch& c = b->corr;
+    if (!c.map) {
+        // no memset: every word is written before it is read (launch_corr)
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.map), corr_map_words(b->n_nrn) * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cnt), b->n_nrn * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.off), b->n_nrn * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cur), b->n_nrn * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cursor), 2 * sizeof(uint32_t)));
+    }
+    if (!c.rows || c.raster_cap < b->spikes.cfg.raster_capacity) {
+        if (c.rows) (void)hipFree(c.rows);
+        c.rows = nullptr;
+        c.raster_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.rows), b->spikes.cfg.raster_capacity * sizeof(uint32_t)));
+        c.raster_cap = b->spikes.cfg.raster_capacity;
+    }
+    if (!c.tally || c.pass_cap < b->spikes.cfg.pass_capacity) {
+        if (c.tally) (void)hipFree(c.tally);
+        c.tally = nullptr;
+        c.pass_cap = 0;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.tally), (uint64_t)b->spikes.cfg.pass_capacity * sizeof(uint2)));
+        c.pass_cap = b->spikes.cfg.pass_capacity;
+    }
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_corr_enqueue(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 7u) == 0, "corr: out_dev must be 8-byte aligned");
+    ST_TRY(corr_check(b, cfg));
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_corr(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->spikes, b->corr, out_dev, (uint32_t)b->cus,
+                        pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_corr(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(corr_check(b, cfg));
+    REQUIRE(words == corr_words(cfg), "abnn_corr: words must equal abnn_corr_words(cfg)");
+    ST_TRY(sync_all(b));
+    if (words > b->corr_cap) {
+        if (b->corr_out) (void)hipFree(b->corr_out);
+        b->corr_out = nullptr;
+        b->corr_cap = 0;
+        ST_TRY(dalloc(&b->corr_out, words));
+        b->corr_cap = words;
+    }
+    HIP_TRY(launch_corr(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->spikes, b->corr, b->corr_out, (uint32_t)b->cus,
+                        b->stream));
+    HIP_TRY(hipMemcpyAsync(out_host, b->corr_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
+    return ABNN_OK;
+}
+
+abnn_status abnn_corr_host(const abnn_corr_config* cfg, uint64_t n_nrn, const abnn_spike_pass* passes, uint64_t n_passes,
+                           const uint32_t* raster, uint64_t n_raster, const abnn_synapse* records, uint64_t n_records,
+                           uint64_t* out)
+{
+    REQUIRE(cfg && out && (passes || n_passes == 0) && (raster || n_raster == 0) && (records || n_records == 0),
+            "null argument");
+    REQUIRE(n_nrn < (1ull << 32) && corr_config_ok(cfg, nullptr) && corr_ranges_ok(*cfg, n_nrn), kCorrConfig);
+    corr_host(*cfg, n_nrn, passes, n_passes, raster, n_raster, records, n_records, out);
     return ABNN_OK;
 }
 

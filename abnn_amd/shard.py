@@ -538,6 +538,30 @@ class ShardedBrain:
     def spike_counts(self, first=None, n=None) -> np.ndarray:
         return self.brain.spike_counts(first, n)
 
+    def load_spikes(self, passes, raster) -> None:
+        self.brain.load_spikes(passes, raster)
+
+    def correlate(self, mode, a=None, b=None, max_lag: int = 16, rows=None, weights=None) -> dict:
+        """Brain.correlate over every shard's records (collective for
+        "synapses": every rank calls it at the same point and gets the whole
+        graph's result).  Every rank's recorder holds the whole network's
+        spikes, so "pop" and "pairs" are the local result; for "synapses"
+        words 4..6 and the plane are summed (all_reduce_sum)."""
+        from . import corr as _corr
+
+        local = self.brain.correlate(mode, a, b, max_lag, rows, weights)
+        cfg = _corr.config(mode, a, b, max_lag, rows, weights)
+        if cfg.mode != _corr.CORR_SYNAPSES:
+            return local
+        words = _corr.to_words(local)
+        t = self._torch.from_numpy(words[4:].view(np.int64).copy()).to(self.xchg.device)
+        t[3] = 0  # word 7 (K) is not a sum
+        self.comm.all_reduce_sum(t)
+        k = words[7]
+        words[4:] = t.cpu().numpy().view(np.uint64)
+        words[7] = k
+        return _corr.decode(words, cfg)
+
     def local_events(self) -> int:
         return self.brain.visited_events()
 

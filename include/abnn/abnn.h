@@ -877,6 +877,109 @@ abnn_status abnn_spikes_get_info(abnn_brain* b, abnn_spikes_info* out);
 abnn_status abnn_spikes_read_passes(abnn_brain* b, uint64_t first, uint64_t n, abnn_spike_pass* out);
 abnn_status abnn_spikes_read_raster(abnn_brain* b, uint64_t first, uint64_t n, uint32_t* out);
 abnn_status abnn_spikes_read_counts(abnn_brain* b, uint64_t first_neuron, uint64_t n, uint32_t* out);
+/* Synchronises and replaces the recorded passes and the raster with the host's:
+ * the state afterwards is as after a clear followed by n_passes recorded
+ * passes.  passes_recorded = n_passes, spikes_recorded = n_raster, the *_dropped
+ * words and the sticky flag zero; the *_seen words and the per-neuron counts are
+ * left as they are.  Refused with ABNN_ERR_INVALID, before anything is written:
+ * no recorder or no raster, a null array that is not empty, n_passes >
+ * pass_capacity, n_raster > raster_capacity, offsets that are not 0, count_0,
+ * count_0 + count_1, ... summing to n_raster, an id at or above N_NRN, an id
+ * outside the recorder's range.                                               */
+abnn_status abnn_spikes_load(abnn_brain* b, const abnn_spike_pass* passes, uint64_t n_passes, const uint32_t* raster, uint64_t n_raster);
+
+/* ---- spike correlograms --------------------------------------
+ * A correlogram of the recorder's raster, computed on the device without moving
+ * the raster or the records to the host.
+ * Rows.  The recorded passes are rows 0 .. K-1 of the pass table; K is
+ * passes_recorded (at most pass_capacity) as it stands in stream order when the
+ * kernels run: it is read on the device.  The window is [row_first, row_first +
+ * row_count) ∩ [0, K); row_count == 0 means "through row K-1".  Row r holds the
+ * entries raster[offset_r + i], i < count_r (offset + count clamped to
+ * raster_capacity); an entry is a neuron id and may repeat within a row.
+ * Lag.  The lag of an ordered pair of entries (e in row p, f in row q) is q - p,
+ * a difference of TABLE ROWS: consecutive rows are consecutive passes (one clock
+ * tick each) unless an abnn_spikes_clear, an abnn_spikes_load or a state restore
+ * came between them; that is not detected.  Pairs with |q - p| <= L = max_lag
+ * count, 0 <= L <= ABNN_CORR_MAX_LAG; both rows lie inside the window.
+ * Populations.  A (the reference, "pre") and B (the target, "post") are ranges
+ * with the u32 test x - first < count; count == 0 means every neuron.  An id at
+ * or above N_NRN (the recorder writes none, abnn_spikes_load refuses them) is
+ * in neither.
+ * Modes.
+ *   ABNN_CORR_POP       H[l + L] = the pairs (e, f) with id(e) in A, id(f) in B
+ *                       and lag l.  Nothing is excluded: at l = 0 an entry whose
+ *                       id is in both ranges pairs with itself.  2L + 1 words.
+ *   ABNN_CORR_PAIRS     the same count split by the two ids: M[((x - a_first) *
+ *                       b_count + (y - b_first)) * (2L + 1) + l + L]; both
+ *                       counts >= 1 and a_count * b_count * (2L + 1) <=
+ *                       ABNN_CORR_MAX_PAIR_WORDS.
+ *   ABNN_CORR_SYNAPSES  H[l + L] = the sum, over the FOLLOWED local records k <
+ *                       n_syn, of the pairs (e, f) with id(e) == src_k, id(f) ==
+ *                       dst_k and lag l: a positive lag is post after pre.  A
+ *                       record is followed when it is live (dst != 0xFFFFFFFF),
+ *                       src < N_NRN and dst < N_NRN, src is in A and dst is in B
+ *                       and, with ABNN_CORR_WEIGHT, w >= w_lo && w < w_hi
+ *                       (abnn_select's rule: NaN never matches).  A followed
+ *                       record is COUPLED when it adds at least one pair.
+ *                       Records at or past n_syn are never read.  The mode
+ *                       equals the sum of M_all[src_k][dst_k][.] over the
+ *                       followed records.
+ * Result: abnn_corr_words(cfg) u64 words, a header of 8 and the plane:
+ *   0 rows used   1 entries in the window   2 entries with id in A   3 ... in B
+ *   4 the sum of the plane   5 followed records   6 coupled records (5, 6:
+ *   SYNAPSES, else 0)   7 K
+ * Every word is an integer sum, so the result depends on neither the grid nor
+ * the order nor the timing (abnn_amd/corr.py restates it in numpy).  Shards: a
+ * rank follows its own records, so a sharded caller adds words 4..6 and the
+ * plane of SYNAPSES over the ranks; every rank's recorder holds the whole
+ * network's spikes, so POP and PAIRS are the same on every rank.  The recorder's
+ * own neuron range applies upstream: a neuron it did not keep has no entries.
+ * Scratch.  The per-row tallies, the one-bit-per-neuron map, three u32 planes of
+ * N_NRN and the row lists (one u32 per raster entry) stay with the handle: the
+ * FIRST correlogram of a handle, and the first after its recorder was restarted
+ * larger, allocates them and may synchronise the device; abnn_brain_destroy
+ * frees them.  Two correlograms of one handle enqueued on different streams
+ * must be ordered by the caller.                                              */
+#define ABNN_CORR_MAX_LAG        256u
+#define ABNN_CORR_MAX_PAIR_WORDS (1ull << 24)
+#define ABNN_CORR_POP       0u
+#define ABNN_CORR_PAIRS     1u
+#define ABNN_CORR_SYNAPSES  2u
+#define ABNN_CORR_WEIGHT    1u   /* flag, SYNAPSES: follow a record only if w_lo <= w && w < w_hi */
+#define ABNN_CORR_HEADER_WORDS 8
+typedef struct abnn_corr_config {        /* 64 bytes */
+    uint32_t a_first, a_count;           /* population A ("pre"); count 0 = every neuron */
+    uint32_t b_first, b_count;           /* population B ("post") */
+    uint64_t row_first, row_count;       /* the window of table rows; count 0 = through row K-1 */
+    uint32_t max_lag;                    /* L: 0 .. ABNN_CORR_MAX_LAG */
+    uint32_t mode;                       /* ABNN_CORR_POP / PAIRS / SYNAPSES */
+    uint32_t flags;                      /* ABNN_CORR_WEIGHT */
+    float    w_lo, w_hi;                 /* as abnn_select_config: +0.0f unless WEIGHT */
+    uint32_t reserved[3];                /* 0 */
+} abnn_corr_config;
+/* The result's words, or 0 for an invalid config (whatever can be checked
+ * without a handle): null, an unknown mode or flag bit, max_lag above the cap,
+ * a range whose first + count exceeds 2^32, PAIRS with a zero count or more
+ * than ABNN_CORR_MAX_PAIR_WORDS plane words, a non-zero w_lo or w_hi without
+ * WEIGHT, a NaN bound or w_lo >= w_hi with it, a reserved word that is not 0. */
+uint64_t    abnn_corr_words(const abnn_corr_config* cfg);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, 8-byte aligned,
+ * abnn_corr_words(cfg) u64) in stream order on `stream`; nothing synchronises
+ * after the handle's first call, so it can sit between passes and between
+ * abnn_engine_run calls.  ABNN_ERR_INVALID: a null argument, an invalid config,
+ * a range that ends above N_NRN, no recorder, a recorder without a raster,
+ * SYNAPSES on a handle whose records are invalid.  n_syn == 0 and K == 0 are
+ * valid and give zero planes.                                                 */
+abnn_status abnn_corr_enqueue(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_corr_words(cfg)).
+ * Its device result stays with the handle until abnn_brain_destroy.           */
+abnn_status abnn_corr(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_host, uint64_t words);
+/* The rule on the host, without a device or a handle, over a pass table and a
+ * raster of a brain of n_nrn neurons (K = n_passes, raster_capacity = n_raster)
+ * and, for SYNAPSES, interchange records (else NULL / 0); out holds
+ * abnn_corr_words(cfg) u64.  ABNN_ERR_INVALID as abnn_corr_enqueue.           */
+abnn_status abnn_corr_host(const abnn_corr_config* cfg, uint64_t n_nrn, const abnn_spike_pass* passes, uint64_t n_passes, const uint32_t* raster, uint64_t n_raster, const abnn_synapse* records, uint64_t n_records, uint64_t* out);
 
 /* ---- neuron timestamps / scalars ----------------------------------------- */
 abnn_status abnn_get_last_fired(abnn_brain* b, uint64_t first, uint64_t* out, uint64_t n);

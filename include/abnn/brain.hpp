@@ -154,6 +154,31 @@ struct HopsView {
     }
 };
 
+// A view of a correlogram (abnn.h abnn_corr: the header and the plane); it does
+// not own the words.
+struct CorrView {
+    const uint64_t* words = nullptr;
+    abnn_corr_config cfg{};
+    CorrView(const uint64_t* w, const abnn_corr_config& c) : words(w), cfg(c) {}
+    uint64_t rows() const { return words[0]; }
+    uint64_t entries() const { return words[1]; }
+    uint64_t in_a() const { return words[2]; }
+    uint64_t in_b() const { return words[3]; }
+    uint64_t total() const { return words[4]; }     // the sum of the plane
+    uint64_t followed() const { return words[5]; }  // SYNAPSES
+    uint64_t coupled() const { return words[6]; }
+    uint64_t recorded() const { return words[7]; }  // K
+    uint32_t bins() const { return 2 * cfg.max_lag + 1; }
+    // POP / SYNAPSES: the pairs at lag l, -max_lag <= l <= max_lag
+    uint64_t at(int64_t lag) const { return words[ABNN_CORR_HEADER_WORDS + (uint64_t)(lag + (int64_t)cfg.max_lag)]; }
+    // PAIRS: the pairs (x in A, y in B) at lag l; x and y are neuron ids
+    uint64_t at(uint32_t x, uint32_t y, int64_t lag) const
+    {
+        return words[ABNN_CORR_HEADER_WORDS + ((uint64_t)(x - cfg.a_first) * cfg.b_count + (y - cfg.b_first)) * bins() +
+                     (uint64_t)(lag + (int64_t)cfg.max_lag)];
+    }
+};
+
 // A view of a snapshot diff result (abnn.h abnn_snapshot_diff: the header and
 // the bins over d = w_now - w_then); it does not own the words.
 struct DiffView {
@@ -667,6 +692,25 @@ public:
     }
     void clear_spikes(bool keep_counts = false) { check(abnn_spikes_clear(h_, keep_counts ? 1 : 0), "abnn_spikes_clear"); }
     void stop_spikes() { check(abnn_spikes_stop(h_), "abnn_spikes_stop"); }
+    // Replace what the recorder holds with a host pass table and its raster (abnn_spikes_load).
+    void load_spikes(const std::vector<abnn_spike_pass>& passes, const std::vector<uint32_t>& raster)
+    {
+        check(abnn_spikes_load(h_, passes.data(), passes.size(), raster.data(), raster.size()), "abnn_spikes_load");
+    }
+    // A correlogram of the recorded spikes on the device (abnn_corr; the rule is
+    // in abnn.h): the result's words, to be read through a CorrView.
+    std::vector<uint64_t> correlate(const abnn_corr_config& cfg) const
+    {
+        const uint64_t words = abnn_corr_words(&cfg);
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_corr(h_, &cfg, w.data(), words), "abnn_corr");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_corr_words(&cfg) u64.
+    void correlate_enqueue(const abnn_corr_config& cfg, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_corr_enqueue(h_, &cfg, out_dev, stream), "abnn_corr_enqueue");
+    }
     abnn_brain* handle() const { return h_; }
     // Before a caller changes the device state through handle() (the
     // device-resident learning loop, engine.hpp): pending Shared-view writes

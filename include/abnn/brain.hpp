@@ -253,7 +253,8 @@ private:
 class Brain {
 public:
     Brain(uint32_t nInput, uint32_t nOutput, uint32_t nHidden, uint32_t nSynapses,
-          uint32_t eventsPerPass, int device = 0, const abnn_params* params = nullptr)
+          uint32_t eventsPerPass, int device = 0, const abnn_params* params = nullptr,
+          uint64_t synCapacity = 0)  // records the handle may grow to (abnn_dims.syn_capacity; 0 = nSynapses)
     {
         abnn_dims d{};
         d.n_input = nInput;
@@ -261,6 +262,7 @@ public:
         d.n_hidden = nHidden;
         d.n_syn = nSynapses;
         d.events_per_pass = eventsPerPass;
+        d.syn_capacity = synCapacity;
         check(abnn_brain_create(&d, params, device, &h_), "abnn_brain_create");
     }
     ~Brain() { abnn_brain_destroy(h_); }

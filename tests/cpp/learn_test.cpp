@@ -7,7 +7,7 @@
 // step, windows.  The GPU side runs the passes in uneven chunks with no
 // synchronise between the calls (handle A); the call-boundary values need a
 // synchronise, so they are read on a second handle (B) run with the same chunks.
-//   usage: learn_test CASE   (1..7, tests/test_learn_gpu.py; prints one JSON line)
+//   usage: learn_test CASE   (1..8, tests/test_learn_gpu.py; prints one JSON line)
 #include <abnn/brain.hpp>
 #include <abnn/engine.hpp>
 
@@ -43,6 +43,7 @@ struct Case {
     uint64_t renorm_thresh;  // 0: the default
     bool hand_back;
     void (*knobs)(abnn_params&) = nullptr;  // brain knobs off the defaults
+    uint64_t cap_extra = 0;                 // syn_capacity = n_syn + cap_extra (structural plasticity)
 };
 
 Case make_case(int id)
@@ -94,6 +95,18 @@ Case make_case(int id)
                 p.eta_reward = 0.5f;
             };
             break;
+        case 8:  // structural plasticity: an update after every 7th pass, so in the middle of the 7-, 64- and
+            // 48-pass calls (the synchronising host part of the update inside abnn_engine_run)
+            c.passes = 120;
+            c.cfg.win_size = 30;
+            c.cap_extra = 2000;
+            c.knobs = [](abnn_params& p) {
+                p.w_prune = 0.105f;
+                p.p_new = 0.35f;
+                p.w_init = 0.5f;
+                p.compact_every = 7;
+            };
+            break;
         default: std::fprintf(stderr, "unknown case %d\n", id); std::exit(2);
     }
     return c;
@@ -134,10 +147,12 @@ int fail(const char* what, long at = -1)
 
 bool brain_matches(abnn::Brain& gpu, CountingOracle& cpu, const char** what)
 {
-    const uint64_t n_syn = cpu.synapses().size();
+    const std::vector<abnn_synapse> ref = cpu.synapses();  // the first n_syn records
+    const uint64_t n_syn = ref.size();
+    if (gpu.n_syn() != n_syn) return *what = "n_syn", false;
     std::vector<abnn::SynapsePacked> w(n_syn);
     abnn::check(abnn_download_synapses(gpu.handle(), 0, reinterpret_cast<abnn_synapse*>(w.data()), n_syn), "download");
-    if (std::memcmp(w.data(), cpu.synapses().data(), n_syn * sizeof(abnn_synapse)) != 0) return *what = "synapses", false;
+    if (n_syn && std::memcmp(w.data(), ref.data(), n_syn * sizeof(abnn_synapse)) != 0) return *what = "synapses", false;
     if (gpu.last_fired() != cpu.all_last_fired()) return *what = "last_fired", false;
     const abnn_scalars sg = gpu.scalars(), sc = cpu.scalars();
     if (sg.clock != sc.clock) return *what = "clock", false;
@@ -157,9 +172,11 @@ int main(int argc, char** argv)
     if (c.renorm_thresh) params.renorm_thresh = c.renorm_thresh;
     if (c.knobs) c.knobs(params);
 
-    abnn::Brain gpu_a(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params);
-    abnn::Brain gpu_b(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params);
-    CountingOracle cpu(c.n_in, c.n_out, c.n_hid, c.n_syn, c.events, &params);
+    abnn::Brain gpu_a(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params,
+                      c.n_syn + c.cap_extra);
+    abnn::Brain gpu_b(c.n_in, c.n_out, (uint32_t)c.n_hid, (uint32_t)c.n_syn, (uint32_t)c.events, 0, &params,
+                      c.n_syn + c.cap_extra);
+    CountingOracle cpu(c.n_in, c.n_out, c.n_hid, c.n_syn, c.events, &params, c.n_syn + c.cap_extra);
     gpu_a.build_random_graph(1);
     gpu_b.build_random_graph(1);
     cpu.build_random_graph(1);
@@ -244,12 +261,17 @@ int main(int argc, char** argv)
         if (!resume_ok) return fail(what, 8);
     }
 
+    abnn_stats st{};
+    abnn::check(abnn_get_stats(gpu_a.handle(), &st), "abnn_get_stats");
+    if (!c.hand_back && (st.pruned != cpu.s_.stats.pruned || st.grown != cpu.s_.stats.grown)) return fail("pruned / grown");
     std::printf("{\"ok\": true, \"case\": %d, \"passes\": %u, \"spikes\": %llu, \"teacher_stamps\": %llu, "
                 "\"windows\": %llu, \"reward_changes\": %llu, \"renorms_gpu\": %llu, \"renorms_cpu\": %llu, "
+                "\"structural_updates\": %llu, \"pruned\": %llu, \"grown\": %llu, \"n_syn\": %llu, "
                 "\"loss\": %.17g, \"reward\": %.9g}\n",
                 id, c.passes, (unsigned long long)spikes, (unsigned long long)cpu.teacher_stamps,
                 (unsigned long long)ec.windows(), (unsigned long long)cpu.reward_changes,
                 (unsigned long long)abnn_renormalisations(gpu_a.handle()), (unsigned long long)cpu.s_.renorms,
-                ec.last_loss(), ec.last_reward());
+                (unsigned long long)abnn_structural_updates(gpu_a.handle()), (unsigned long long)st.pruned,
+                (unsigned long long)st.grown, (unsigned long long)gpu_a.n_syn(), ec.last_loss(), ec.last_reward());
     return 0;
 }

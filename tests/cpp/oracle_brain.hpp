@@ -3,6 +3,7 @@
 // driver code runs over the GPU brain and over the oracle.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <vector>
@@ -11,14 +12,18 @@
 
 struct OracleBrain {
     OracleBrain(uint32_t n_in, uint32_t n_out, uint64_t n_hid, uint64_t n_syn, uint64_t events,
-                const abnn_params* params = nullptr)
+                const abnn_params* params = nullptr, uint64_t syn_capacity = 0)
     {
         s_ = oracle_state{};
         if (params) s_.p = *params;
         else oracle_default_params(&s_.p);
-        s_.dims = abnn_dims{n_in, n_out, n_hid, n_syn, events, 0, 0};
+        const uint64_t cap = std::max(syn_capacity, n_syn);  // 0 = the creation size (as the C-ABI)
+        s_.dims = abnn_dims{n_in, n_out, n_hid, n_syn, events, 0, 0, cap};
         s_.n_nrn = (uint64_t)n_in + n_out + n_hid;
-        syn_.resize(n_syn);
+        syn_.resize(cap);
+        // structural plasticity: the grown slots of one period, zeroed (as oracle/oracle.py)
+        grown_.assign(std::max<uint64_t>(1, (uint64_t)s_.p.compact_every * s_.p.max_spikes), abnn_synapse{});
+        s_.grown = grown_.data();
         lf_.assign(s_.n_nrn, 0);
         lv_.assign(s_.n_nrn, 0);
         s_.syn = syn_.data();
@@ -28,7 +33,7 @@ struct OracleBrain {
     }
     void build_random_graph(uint64_t seed = 1)
     {
-        oracle_gen_synapses(syn_.data(), 0, syn_.size(), s_.dims.n_input, s_.dims.n_output, s_.n_nrn, seed, 4);
+        oracle_gen_synapses(syn_.data(), 0, s_.dims.n_syn, s_.dims.n_input, s_.dims.n_output, s_.n_nrn, seed, 4);
     }
     uint32_t n_input() const { return s_.dims.n_input; }
     uint32_t n_output() const { return s_.dims.n_output; }
@@ -61,11 +66,13 @@ struct OracleBrain {
     template <class OS> void save(OS&) const { throw std::runtime_error("not used"); }
     template <class IS> void load(IS&) { throw std::runtime_error("not used"); }
 
-    const std::vector<abnn_synapse>& synapses() const { return syn_; }
+    // the current records (n_syn changes at structural updates; syn_ holds the capacity)
+    std::vector<abnn_synapse> synapses() const { return {syn_.begin(), syn_.begin() + (ptrdiff_t)s_.dims.n_syn}; }
+    uint64_t n_syn() const { return s_.dims.n_syn; }
     const std::vector<uint64_t>& all_last_fired() const { return lf_; }
     float rbar() const { return s_.rbar; }
 
     oracle_state s_;
-    std::vector<abnn_synapse> syn_;
+    std::vector<abnn_synapse> syn_, grown_;
     std::vector<uint64_t> lf_, lv_;
 };

@@ -5,7 +5,8 @@ BrainEngine<OracleBrain> on the CPU oracle (tests/cpp/learn_test.cpp), bit for
 bit: every pass's outputs and normalised rates, loss / reward at every call
 boundary, the final weights, lastFired, scalars and driver state; the GPU side
 runs uneven chunks with no synchronise between the calls.
-Python: LearnEngine, one call against two, and the error returns."""
+Python: LearnEngine, one call against two, the error returns, and the census
+inside the loop across structural updates."""
 import json
 import subprocess
 
@@ -80,6 +81,18 @@ def test_window_pre_1_with_a_large_reward_term(gpu):
     assert res["renorms_gpu"] == res["renorms_cpu"] and res["renorms_cpu"] >= 1
 
 
+@pytest.mark.gpu
+def test_structural_updates_inside_the_loop(gpu):
+    """Pruning and synaptogenesis on, an update after every 7th pass: 17 updates
+    in 120 passes, in the middle of the 7-, 64- and 48-pass calls (the update's
+    synchronising host part runs inside abnn_engine_run).  The program's
+    bit-for-bit comparison covers n_syn and the pruned / grown counts."""
+    res = _run_case(8)
+    assert res["passes"] == 120 and res["windows"] == 4 and res["spikes"] > 0
+    assert res["structural_updates"] == 17
+    assert res["pruned"] > 0 and res["grown"] > 0
+
+
 def _stimulus(frames, n_in=256, n_out=256, dt=0.0009, hz=0.5):
     """FunctionalDataset's frames (functional-dataset.cpp:24-52) as test_engine._frames
     makes them, vectorised: cos^2 input, 0.5 sin + 0.5 target, libm's cosf / sinf."""
@@ -100,7 +113,7 @@ def _stimulus(frames, n_in=256, n_out=256, dt=0.0009, hz=0.5):
 
 @pytest.fixture(scope="module")
 def stimulus():
-    xin, xex = _stimulus(60)
+    xin, xex = _stimulus(120)
     xin.setflags(write=False)
     xex.setflags(write=False)
     return xin, xex
@@ -172,3 +185,57 @@ def test_python_error_returns(gpu, stimulus):
         abnn_amd.LearnEngine(shard)
     assert err.value.status == 1
     shard.close()
+
+
+def _plastic_brain():
+    import abnn_amd
+
+    b = abnn_amd.Brain(256, 256, 488, 10_000, 100_000, syn_capacity=12_000,  # config 1, learn_test case 8
+                       w_prune=0.105, p_new=0.35, w_init=0.5, compact_every=7)
+    b.build_random_graph(1)
+    return b
+
+
+@pytest.mark.gpu
+def test_python_census_follows_structural_updates(gpu, stimulus):
+    """set_census(every=7) on a brain whose structural updates fall on the same
+    steps: each census counts the records as the update of its step left them
+    (live + tombstones = n_syn then), which a second handle stepped from the
+    host one pass per call reports after every step; the last one, taken at
+    the run's end, is Brain.census()."""
+    import abnn_amd
+
+    xin, xex = stimulus
+    steps_total = 119  # 17 x 7: the last census closes the run
+    b = _plastic_brain()
+    with abnn_amd.LearnEngine(b, win_size=30) as e:
+        e.set_census(16, 0.0, 1.0, every=7, capacity=32)
+        at = 0
+        for n in (1, 7, 64, 47):  # updates and censuses in the middle of the calls
+            e.run(xin[at:at + n], xex[at:at + n])
+            at += n
+        assert at == steps_total and e.census_count() == 17
+        steps, got = e.census_trace(0, 17)
+        final = b.census(16, 0.0, 1.0)
+    assert b.structural_updates() == 17
+
+    h = _plastic_brain()
+    sizes = []
+    with abnn_amd.LearnEngine(h, win_size=30) as e:
+        for k in range(steps_total):
+            e.run(xin[k:k + 1], xex[k:k + 1])
+            sizes.append(h.n_syn())  # host mirror, as the update of step k + 1 left it
+    assert steps.tolist() == [7 * (i + 1) for i in range(17)]
+    for s, c in zip(steps.tolist(), got):
+        assert c["records"] == c["live"] + c["tombstones"] == sizes[s - 1], s
+        assert c["tombstones"] == 0, s  # taken right after the update of its step
+    assert len(set(sizes)) > 1 and b.n_syn() == h.n_syn() == sizes[-1]
+    assert b.checksum() == h.checksum() and b.stats() == h.stats()
+    st = b.stats()
+    assert st["pruned"] > 0 and st["grown"] > 0
+    last = got[-1]
+    assert {k: v for k, v in last.items() if k not in ("counts", "edges")} == \
+        {k: v for k, v in final.items() if k not in ("counts", "edges")}
+    assert np.array_equal(last["counts"], final["counts"])
+    b.close()
+    h.close()

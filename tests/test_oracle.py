@@ -335,6 +335,43 @@ def test_structural_plasticity_matches_python_restatement(mode, events):
     assert len(set(sizes)) > 1  # the graph changed size
 
 
+# The capacity cases of tests/test_gpu_structural_edges.py (every spike grows:
+# p_new = 1): at the update after pass 3 the 2560 grown records meet a room of
+# cap_extra, so the oracle's "while capacity lasts" cuts the append -- at
+# cap_extra 0, 1 and 7 inside the first 1024-slot block that holds used slots,
+# at 1000 (compact_every 2) and 1500 (compact_every 1) inside a later one.
+@pytest.mark.parametrize("mode,events,cap_extra,w_prune,ce", [
+    (0, 120_000, 0, 0.105, 2), (0, 120_000, 1, 0.105, 2), (0, 120_000, 7, 0.105, 2), (0, 120_000, 1000, 0.105, 2),
+    (0, 120_000, 1500, 0.105, 1), (0, 120_000, 1, 0.0, 2), (1, 60_000, 7, 0.0, 2)])
+def test_structural_capacity_cut_matches_python_restatement(mode, events, cap_extra, w_prune, ce):
+    over = dict(SP, p_new=1.0, w_prune=w_prune, compact_every=ce)
+    ob = _sp_brain(mode, cap_extra=cap_extra, events=events, **over)
+    emu = _emu_from(ob, ob.s.dims.events_per_pass)
+    emu.p.update(over)
+    emu.capacity = cap = int(ob.s.dims.syn_capacity)
+    emu.stim = (0, 256)
+    cut, fired0 = False, 0
+    for k in range(8):
+        live = int((ob.syn["src"] != 0xFFFFFFFF).sum())
+        pruned0 = ob.stats()["pruned"]
+        ob.pass_serial()
+        emu.one_pass()
+        assert int(ob.s.dims.n_syn) == len(emu.src) <= cap, k
+        assert np.array_equal(ob.syn["src"], np.array(emu.src, dtype=np.uint32)), k
+        assert np.array_equal(ob.syn["dst"], np.array(emu.dst, dtype=np.uint32)), k
+        _compare(ob, emu)
+        if (k + 1) % ce == 0:
+            st = ob.stats()
+            attempts, fired0 = st["fired"] - fired0, st["fired"]
+            room = cap - (live - (st["pruned"] - pruned0))
+            if attempts > room:  # some slots are dropped: the array is full
+                cut = True
+                assert int(ob.s.dims.n_syn) == cap, (k, attempts, room)
+    assert cut
+    st = ob.stats()
+    assert st["grown"] == emu.n_grown > 0 and st["pruned"] == emu.pruned
+
+
 @pytest.mark.parametrize("tombs,expect", [
     # D = 2, m = 18: the holes 2 and 4 take the tail's 18 and 19
     ([2, 4], [0, 1, 18, 3, 19] + list(range(5, 18))),

@@ -234,16 +234,23 @@ abnn_status dalloc(T** p, uint64_t count)
         if (_s != ABNN_OK) return _s;       \
     } while (0)
 
-abnn_status ensure_idx_scratch(abnn_brain* b, uint64_t n)
+// A device buffer that grows to the largest count asked: *p holds *cap entries.
+template <typename T>
+abnn_status grow(T** p, uint64_t* cap, uint64_t count)
 {
-    if (n <= b->idx_cap) return ABNN_OK;
-    if (b->idx_scratch) (void)hipFree(b->idx_scratch);
-    b->idx_scratch = nullptr;
-    b->idx_cap = 0;
-    ST_TRY(dalloc(&b->idx_scratch, n));
-    b->idx_cap = n;
+    if (count <= *cap) return ABNN_OK;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    ST_TRY(dalloc(p, count));
+    *cap = count;
     return ABNN_OK;
 }
+
+abnn_status ensure_idx_scratch(abnn_brain* b, uint64_t n) { return grow(&b->idx_scratch, &b->idx_cap, n); }
+
+// a src / dst range of a config: not set (count 0), or inside [0, n_nrn)
+inline bool range_ok(uint32_t first, uint32_t count, uint64_t n_nrn) { return !count || (uint64_t)first + count <= n_nrn; }
 
 // Device records are the packed src streams, dst and w (SynArrays, engine.h);
 // abnn_synapse is the host interchange format.  Capacity `count` records.
@@ -1211,8 +1218,8 @@ abnn_status census_check(const abnn_brain* b, const abnn_census_config* cfg, flo
     REQUIRE(b && cfg, "null argument");
     REQUIRE(census_config_ok(cfg, scale),
             "census: bins must be 1..4096, lo < hi both finite with a finite bins / (hi - lo), reserved 0");
-    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= b->n_nrn, "census: src range ends above N_NRN");
-    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= b->n_nrn, "census: dst range ends above N_NRN");
+    REQUIRE(range_ok(cfg->src_first, cfg->src_count, b->n_nrn), "census: src range ends above N_NRN");
+    REQUIRE(range_ok(cfg->dst_first, cfg->dst_count, b->n_nrn), "census: dst range ends above N_NRN");
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     return ABNN_OK;
 }
@@ -1277,13 +1284,7 @@ abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* 
     ST_TRY(degree_check(b, cfg));
     REQUIRE(words == degree_words(cfg, b->n_nrn), "abnn_degree: words must equal abnn_degree_words(cfg, N_NRN)");
     ST_TRY(sync_all(b));
-    if (words > b->degree_cap) {
-        if (b->degree_out) (void)hipFree(b->degree_out);
-        b->degree_out = nullptr;
-        b->degree_cap = 0;
-        ST_TRY(dalloc(&b->degree_out, words));
-        b->degree_cap = words;
-    }
+    ST_TRY(grow(&b->degree_out, &b->degree_cap, words));
     HIP_TRY(launch_degree(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->degree_out, (uint32_t)b->cus, b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->degree_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1304,8 +1305,8 @@ abnn_status select_check(abnn_brain* b, const abnn_select_config* cfg, uint64_t 
     REQUIRE(select_words(cfg, capacity) != 0,
             "select: unknown flags, reserved != 0, w_lo / w_hi without WEIGHT, a NaN bound or w_lo >= w_hi, "
             "ANY with no range set, or a range that wraps u32");
-    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= b->n_nrn, "select: src range ends above N_NRN");
-    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= b->n_nrn, "select: dst range ends above N_NRN");
+    REQUIRE(range_ok(cfg->src_first, cfg->src_count, b->n_nrn), "select: src range ends above N_NRN");
+    REQUIRE(range_ok(cfg->dst_first, cfg->dst_count, b->n_nrn), "select: dst range ends above N_NRN");
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     HIP_TRY(hipSetDevice(b->device));
     // no memset: a select zeroes the counts it reads and writes the offsets it reads
@@ -1379,8 +1380,8 @@ constexpr const char* kEditInvalid =
 abnn_status edit_check(const abnn_edit_config* cfg, uint64_t n_nrn, bool has_plane)
 {
     REQUIRE(edit_words(cfg) != 0, kEditInvalid);
-    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= n_nrn, "edit: src range ends above N_NRN");
-    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= n_nrn, "edit: dst range ends above N_NRN");
+    REQUIRE(range_ok(cfg->src_first, cfg->src_count, n_nrn), "edit: src range ends above N_NRN");
+    REQUIRE(range_ok(cfg->dst_first, cfg->dst_count, n_nrn), "edit: dst range ends above N_NRN");
     REQUIRE(n_nrn <= kMaxNeurons, "edit: N_NRN above the library's limit");
     REQUIRE(edit_is_scale(cfg->op) == has_plane, "edit: a SCALE op needs a plane, every other op none");
     return ABNN_OK;
@@ -1411,13 +1412,7 @@ abnn_status abnn_edit(abnn_brain* b, const abnn_edit_config* cfg, const float* p
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     ST_TRY(sync_all(b));
     if (!b->edit_out) ST_TRY(dalloc(&b->edit_out, ABNN_EDIT_HEADER_WORDS));
-    if (plane_count > b->edit_plane_cap) {
-        if (b->edit_plane) (void)hipFree(b->edit_plane);
-        b->edit_plane = nullptr;
-        b->edit_plane_cap = 0;
-        ST_TRY(dalloc(&b->edit_plane, plane_count));
-        b->edit_plane_cap = plane_count;
-    }
+    ST_TRY(grow(&b->edit_plane, &b->edit_plane_cap, plane_count));
     if (plane_count)
         HIP_TRY(hipMemcpyAsync(b->edit_plane, plane_host, plane_count * sizeof(float), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(launch_edit(b->d.syn, b->dims.n_syn, edit_rule(*cfg, b->n_nrn, b->dims.syn_offset),
@@ -1510,8 +1505,8 @@ constexpr const char* kDiffInvalid =
 abnn_status diff_check(const abnn_diff_config* cfg, uint64_t n_nrn, float* scale)
 {
     REQUIRE(diff_config_ok(cfg, scale), kDiffInvalid);
-    REQUIRE(!cfg->src_count || (uint64_t)cfg->src_first + cfg->src_count <= n_nrn, "snapshot diff: src range ends above N_NRN");
-    REQUIRE(!cfg->dst_count || (uint64_t)cfg->dst_first + cfg->dst_count <= n_nrn, "snapshot diff: dst range ends above N_NRN");
+    REQUIRE(range_ok(cfg->src_first, cfg->src_count, n_nrn), "snapshot diff: src range ends above N_NRN");
+    REQUIRE(range_ok(cfg->dst_first, cfg->dst_count, n_nrn), "snapshot diff: dst range ends above N_NRN");
     return ABNN_OK;
 }
 
@@ -1760,13 +1755,7 @@ abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_
     ST_TRY(hops_check(b, cfg));
     REQUIRE(words == hops_words(cfg, b->n_nrn), "abnn_hops: words must equal abnn_hops_words(cfg, N_NRN)");
     ST_TRY(sync_all(b));
-    if (words > b->hops_cap) {
-        if (b->hops_out) (void)hipFree(b->hops_out);
-        b->hops_out = nullptr;
-        b->hops_cap = 0;
-        ST_TRY(dalloc(&b->hops_out, words));
-        b->hops_cap = words;
-    }
+    ST_TRY(grow(&b->hops_out, &b->hops_cap, words));
     ST_TRY(hops_steps(b, cfg, b->hops_out, b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->hops_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
     HIP_TRY(hipStreamSynchronize(b->stream));
@@ -1978,13 +1967,7 @@ abnn_status abnn_corr(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_
     ST_TRY(corr_check(b, cfg));
     REQUIRE(words == corr_words(cfg), "abnn_corr: words must equal abnn_corr_words(cfg)");
     ST_TRY(sync_all(b));
-    if (words > b->corr_cap) {
-        if (b->corr_out) (void)hipFree(b->corr_out);
-        b->corr_out = nullptr;
-        b->corr_cap = 0;
-        ST_TRY(dalloc(&b->corr_out, words));
-        b->corr_cap = words;
-    }
+    ST_TRY(grow(&b->corr_out, &b->corr_cap, words));
     HIP_TRY(launch_corr(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->spikes, b->corr, b->corr_out, (uint32_t)b->cus,
                         b->stream));
     HIP_TRY(hipMemcpyAsync(out_host, b->corr_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));

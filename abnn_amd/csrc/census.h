@@ -11,19 +11,6 @@ namespace abnn {
 
 constexpr int kCensusThreads = 512;          // 8 waves per workgroup
 constexpr int kCensusUnroll = 4;             // 16-B loads in flight per lane
-constexpr uint32_t kCensusLdsWords = 16384;  // 64 KiB of u32 counters per workgroup
-constexpr uint32_t kCensusMaxCopies = 32;    // histogram copies, chosen by lane & (copies - 1)
-// a workgroup's LDS counters are u32: no workgroup scans more records than this
-constexpr uint64_t kCensusMaxPerWg = 1ull << 31;
-
-// Histogram copies for `bins` bins: the most (a power of two, at most one per
-// LDS bank) that fit the workgroup's counters.  4096 bins -> 4, <= 512 -> 32.
-inline uint32_t census_copies(uint32_t bins)
-{
-    uint32_t r = kCensusMaxCopies;
-    while (r > 1 && (uint64_t)bins * r > kCensusLdsWords) r >>= 1;
-    return r;
-}
 
 // The checks of abnn_census_words (everything that needs no handle); *scale =
 // (float)bins / (hi - lo), one fp32 division.

@@ -4,39 +4,27 @@
 // count (or an order key's extreme), so the result does not depend on the
 // grid, the order or the atomics; abnn_amd/census.py restates it in numpy.
 //
-//   k_census<kSrc> : each lane loads 16 B = two {dst, w} records at a time
-//       (kCensusUnroll loads in flight), non-temporal: the records are read
-//       once.  Only the kSrc instantiation (a src range is set) reads the two
-//       src streams.  Header counts and the min / max keys stay in registers;
-//       bin counts go to a workgroup histogram in LDS, flushed once with global
-//       u64 atomics (zero bins skipped), then the header with one atomic per
-//       word and workgroup.  Workgroups are independent: no look-back, no
-//       ticket, no residency assumption.
+//   k_census<kSrc> : the stream is scan.h's RecordStream, read by the kernel's
+//       own loop (kCensusUnroll 16-B pair loads per lane and iteration; kSrc: a
+//       src range is set), the odd last record by odd_record().  Header counts
+//       and the min / max keys stay in registers; bin counts go to scan.h's
+//       bank-spread histogram in LDS, flushed once with global u64 atomics,
+//       then the header with one atomic per word and workgroup.  Workgroups
+//       are independent: no look-back, no ticket, no residency assumption.
 //   k_census_finish : one thread, in stream order after it: writes word 0 and
 //       turns the two keys into f32 bits.
-//
-// Contention.  A weight distribution that falls into a few bins (the generated
-// graph: 6-7 of 64; a constant weight: one) would serialise a single LDS
-// histogram on those addresses.  The workgroup therefore keeps `copies`
-// histograms (census_copies: 32 up to 512 bins, 4 at 4096), interleaved as
-// hist[bin * copies + (lane & (copies - 1))]: with 32 copies the 32 lanes an
-// LDS atomic services together always hit 32 different banks, whatever their
-// bins are; with fewer, equal bins from different lanes still spread over
-// `copies` banks (a constant weight at 4096 bins: 8 lanes per address).
 #include "census.h"
+#include "scan.h"
 
 #pragma clang fp contract(off)
 
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+constexpr uint32_t kCensusHead = 7;  // header sums per wave (wave_words_to_lds packs them at this stride)
 
 struct CensusArgs {
-    const u32x4* dw4;  // the {dst, w} stream, two records per element
-    const uint2* dw;
-    const uint16_t* lo;
-    const uint8_t* hi;
+    RecordStream s;
     unsigned long long* out;
     uint64_t n;
     float w_lo, w_hi, scale;
@@ -65,7 +53,7 @@ template <bool kSrc>
 __device__ __forceinline__ void tally(const CensusArgs& a, uint32_t* hist, uint32_t copy, uint32_t src, uint32_t dst,
                                       uint32_t wbits, Tally& t)
 {
-    const bool tomb = dst == 0xFFFFFFFFu;
+    const bool tomb = dst == kAbsentDst;
     t.tomb += tomb ? 1u : 0u;
     bool sel = !tomb && dst - a.dst_first < a.dst_span;
     if (kSrc) sel = sel && src - a.src_first < a.src_span;
@@ -89,28 +77,13 @@ __device__ __forceinline__ void tally(const CensusArgs& a, uint32_t* hist, uint3
     }
     uint32_t bin = (uint32_t)((w - a.w_lo) * a.scale);
     bin = bin < a.bins - 1 ? bin : a.bins - 1;
-    __hip_atomic_fetch_add(&hist[bin * a.copies + copy], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) {
-        const uint32_t o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
+    hist_add(hist, a.copies, copy, bin);
 }
 
 template <bool kSrc>
 __global__ __launch_bounds__(kCensusThreads) void k_census(CensusArgs a)
 {
-    extern __shared__ uint32_t hist[];  // [bins * copies], at least 8 words per wave
+    extern __shared__ uint32_t hist[];  // [bins * copies], at least kCensusHead words per wave
     constexpr uint32_t T = kCensusThreads, U = kCensusUnroll;
     const uint32_t tid = threadIdx.x;
     const uint32_t words = a.bins * a.copies;
@@ -119,19 +92,25 @@ __global__ __launch_bounds__(kCensusThreads) void k_census(CensusArgs a)
 
     const uint32_t copy = tid & (a.copies - 1);
     Tally t{0, 0, 0, 0, 0, 0xFFFFFFFFu, 0u};
-    const uint64_t n_pairs = a.n >> 1;
+    const uint64_t n_pairs = a.n >> 1;  // whole pairs
     const uint64_t stride = (uint64_t)gridDim.x * (T * U);
     for (uint64_t base = (uint64_t)blockIdx.x * (T * U); base < n_pairs; base += stride) {
+        // The loads stay written out here, not PairLoad's: with these, the
+        // compiler lets a lane's loads wait for one another, and that is the
+        // schedule the census's speed at four workgroups per CU rests on
+        // (profiles/scan_refactor_ab.txt).  PairLoad keeps all U in flight:
+        // another load policy.  A change of the record layout must be made
+        // here and in k_diff (snapshot.hip) as well as in scan.h.
         u32x4 v[U];
         uint32_t lo2[U], hi2[U];
 #pragma unroll
-        for (uint32_t k = 0; k < U; ++k) {  // every load of the iteration before its first use
+        for (uint32_t k = 0; k < U; ++k) {
             const uint64_t p = base + k * T + tid;
             if (p < n_pairs) {
-                v[k] = __builtin_nontemporal_load(a.dw4 + p);
+                v[k] = __builtin_nontemporal_load(a.s.dw4 + p);
                 if (kSrc) {
-                    lo2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.lo) + p);
-                    hi2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(a.hi) + p);
+                    lo2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.s.lo) + p);
+                    hi2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(a.s.hi) + p);
                 }
             }
         }
@@ -149,33 +128,24 @@ __global__ __launch_bounds__(kCensusThreads) void k_census(CensusArgs a)
             }
         }
     }
-    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {  // the record no pair holds
-        const uint64_t i = a.n - 1;
-        const uint2 r = a.dw[i];
-        tally<kSrc>(a, hist, copy, kSrc ? code_src(a.lo[i], a.hi[hi_pos(i)]) : 0u, r.x, r.y, t);
+    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {
+        const OddRecord r = odd_record<kSrc>(a.s, a.n);
+        tally<kSrc>(a, hist, copy, r.src, r.dst, r.w, t);
     }
     __syncthreads();
 
-    // flush: a thread sums the copies of its bins, starting at its own copy so
-    // that the lanes of a wave read different banks
-    for (uint32_t b = tid; b < a.bins; b += T) {
-        uint32_t s = 0;
-        for (uint32_t r = 0; r < a.copies; ++r) s += hist[b * a.copies + ((r + tid) & (a.copies - 1))];
-        if (s) atomicAdd(a.out + ABNN_CENSUS_HEADER_WORDS + b, (unsigned long long)s);
-    }
+    hist_flush(hist, a.bins, a.copies, tid, T, a.out + ABNN_CENSUS_HEADER_WORDS);
     __syncthreads();  // the histogram is reused for the waves' header sums
 
     // words 6 / 7 hold max(~min key) and max(max key) until k_census_finish:
     // both start at the zeros the buffer was cleared to
-    const uint32_t h[7] = {wave_add(t.tomb), wave_add(t.sel),   wave_add(t.under), wave_add(t.over),
-                           wave_add(t.nan),  wave_max(~t.kmin), wave_max(t.kmax)};
-    if ((tid & 63) == 0)
-        for (uint32_t j = 0; j < 7; ++j) hist[(tid >> 6) * 8 + j] = h[j];
-    __syncthreads();
-    if (tid < 7) {
+    const uint32_t h[kCensusHead] = {wave_add(t.tomb), wave_add(t.sel),   wave_add(t.under), wave_add(t.over),
+                                     wave_add(t.nan),  wave_max(~t.kmin), wave_max(t.kmax)};
+    wave_words_to_lds(hist, h, tid);
+    if (tid < kCensusHead) {
         unsigned long long s = 0;
         for (uint32_t w = 0; w < T / 64; ++w) {
-            const uint32_t x = hist[w * 8 + tid];
+            const uint32_t x = hist[w * kCensusHead + tid];
             s = tid < 5 ? s + x : (x > s ? x : s);
         }
         if (s) {
@@ -207,35 +177,24 @@ hipError_t launch_census(const SynArrays& syn, uint64_t n, const abnn_census_con
     unsigned long long* out = reinterpret_cast<unsigned long long*>(out_dev);
     if (n > 0) {
         CensusArgs a{};
-        a.dw4 = reinterpret_cast<const u32x4*>(syn.dw);
-        a.dw = syn.dw;
-        a.lo = syn.lo;
-        a.hi = syn.hi;
+        a.s = record_stream(syn);
         a.out = out;
         a.n = n;
         a.w_lo = cfg.lo;
         a.w_hi = cfg.hi;
         a.scale = scale;
         a.bins = cfg.bins;
-        a.copies = census_copies(cfg.bins);
+        a.copies = hist_copies(cfg.bins);
         a.src_first = cfg.src_first;
         a.src_span = cfg.src_count ? cfg.src_count : 0xFFFFFFFFu;
         a.dst_first = cfg.dst_count ? cfg.dst_first : 0u;
         a.dst_span = cfg.dst_count ? cfg.dst_count : 0xFFFFFFFFu;
-        const uint32_t lds_words = std::max<uint32_t>(a.bins * a.copies, (kCensusThreads / 64) * 8);
-        // grid from the CU count: as many workgroups per CU as their histograms
-        // leave room for (160 KiB of LDS per CU), at most 4 (32 waves)
-        const uint32_t per_cu = std::min<uint32_t>(4u, (160u * 1024u) / (lds_words * 4u));
-        const uint64_t per_iter = 2ull * kCensusThreads * kCensusUnroll;  // records per workgroup iteration
-        const uint64_t iters = (n + per_iter - 1) / per_iter;
-        uint64_t grid = std::min<uint64_t>((uint64_t)std::max(1u, cus) * per_cu, iters);
-        // u32 LDS counters: no workgroup scans more than kCensusMaxPerWg records
-        const uint64_t max_iters = kCensusMaxPerWg / per_iter;
-        if ((iters + grid - 1) / grid > max_iters) grid = (iters + max_iters - 1) / max_iters;
+        const uint32_t lds_words = std::max<uint32_t>(a.bins * a.copies, (kCensusThreads / 64) * kCensusHead);
+        const uint32_t grid = scan_grid(n, 2ull * kCensusThreads * kCensusUnroll, lds_words, cus, kScanMaxPerWg);
         if (cfg.src_count)
-            hipLaunchKernelGGL(k_census<true>, dim3((uint32_t)grid), dim3(kCensusThreads), lds_words * 4, s, a);
+            hipLaunchKernelGGL(k_census<true>, dim3(grid), dim3(kCensusThreads), lds_words * 4, s, a);
         else
-            hipLaunchKernelGGL(k_census<false>, dim3((uint32_t)grid), dim3(kCensusThreads), lds_words * 4, s, a);
+            hipLaunchKernelGGL(k_census<false>, dim3(grid), dim3(kCensusThreads), lds_words * 4, s, a);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -41,11 +41,11 @@
 //       histogram of 2L + 1 u64 bins, flushed once per workgroup with atomics.
 //       The records that no whole 16-B load holds are read one at a time.
 #include "corr.h"
+#include "scan.h"
 
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
 
@@ -71,12 +71,6 @@ __device__ __forceinline__ void window_of(const CorrArgs& a, uint64_t* K, uint64
     k = k < a.pass_cap ? k : a.pass_cap;
     *K = k;
     corr_window(a.r, k, lo, hi);
-}
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 __device__ __forceinline__ void add64(u64* p, u64 v)

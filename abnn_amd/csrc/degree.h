@@ -17,8 +17,6 @@ constexpr uint32_t kDegreeNarrowMax = 4096;
 // a narrow launch's accumulators fit this; a range whose four planes do not
 // (more than 2730 neurons) is scanned once per direction
 constexpr uint32_t kDegreeLdsBytes = 64 * 1024;
-// a workgroup's LDS degree counters are u32: no workgroup scans more records than this
-constexpr uint64_t kDegreeMaxPerWg = 1ull << 31;
 
 constexpr uint32_t kDegreeAll = ABNN_DEG_OUT | ABNN_DEG_IN | ABNN_DEG_OUT_W | ABNN_DEG_IN_W;
 

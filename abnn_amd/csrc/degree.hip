@@ -5,10 +5,9 @@
 // result word is an integer sum, so the result does not depend on the grid, the
 // order or the atomics; abnn_amd/degree.py restates it in numpy.
 //
-//   k_degree<kOut, kIn, kWide> : the stream is k_census's: each lane loads 16 B
-//       = two {dst, w} records at a time (kDegreeUnroll loads in flight),
-//       non-temporal; only the kOut instantiations read the two src streams.
-//       Header counts stay in registers and leave with one atomic per word and
+//   k_degree<kOut, kIn, kWide> : the stream is scan.h's (kDegreeUnroll loads
+//       in flight; the kOut instantiations read the two src streams).  Header
+//       counts stay in registers and leave with one atomic per word and
 //       workgroup.  Workgroups are independent: no look-back, no ticket, no
 //       residency assumption.
 //     narrow (!kWide, R of at most kDegreeNarrowMax neurons): the planes of R
@@ -30,22 +29,20 @@
 // (below 2^39 in magnitude), so one scan serves both.  A wave with no record in
 // R skips all of it, and a wave whose items are all different skips the scan.
 #include "degree.h"
+#include "scan.h"
 
 #pragma clang fp contract(off)
 
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kNone = 0xFFFFFFFFu;    // a record outside R, a tombstone, no record
+constexpr uint32_t kNone = kAbsentDst;      // a record outside R, a tombstone, no record
 constexpr uint32_t kNoPush = 0xFFFFFFFEu;  // "this lane hands nothing back"
 
+constexpr uint32_t kDegreeHead = 5;  // header sums per wave (wave_words_to_lds packs them at this stride)
+
 struct DegreeArgs {
-    const u32x4* dw4;  // the {dst, w} stream, two records per element
-    const uint2* dw;
-    const uint16_t* lo;
-    const uint8_t* hi;
+    RecordStream s;
     unsigned long long* out;
     uint64_t n;
     uint32_t first, m;    // R = [first, first + m)
@@ -182,16 +179,10 @@ __device__ __forceinline__ void items(const DegreeArgs& a, bool valid, uint32_t 
     }
 }
 
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 template <bool kOut, bool kIn, bool kWide>
 __global__ __launch_bounds__(kDegreeThreads) void k_degree(DegreeArgs a, uint32_t lds_words)
 {
-    extern __shared__ uint32_t lds[];  // narrow: the planes of R; then 8 words per wave
+    extern __shared__ uint32_t lds[];  // narrow: the planes of R; then kDegreeHead words per wave
     constexpr uint32_t T = kDegreeThreads, U = kDegreeUnroll;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     if (!kWide) {
@@ -200,45 +191,18 @@ __global__ __launch_bounds__(kDegreeThreads) void k_degree(DegreeArgs a, uint32_
     }
 
     Tally t{0, {0, 0}, {0, 0}};
-    const uint64_t n_pairs = (a.n + 1) >> 1;  // the last one holds one record when n is odd
+    const uint64_t n_pairs = scan_pairs(a.n);
     const uint64_t stride = (uint64_t)gridDim.x * (T * U);
     // the loop and everything in it is uniform over the wave: a lane past the
     // end carries two absent records through scatter()'s shuffles
     for (uint64_t base = (uint64_t)blockIdx.x * (T * U); base < n_pairs; base += stride) {
-        u32x4 v[U];
-        uint32_t lo2[U], hi2[U];
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) {  // every load of the iteration before its first use
-            const uint64_t p = base + k * T + tid;
-            v[k] = u32x4{kNone, 0u, kNone, 0u};
-            lo2[k] = hi2[k] = 0;
-            if (2 * p + 1 < a.n) {
-                v[k] = __builtin_nontemporal_load(a.dw4 + p);
-                if (kOut) {
-                    lo2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.lo) + p);
-                    hi2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(a.hi) + p);
-                }
-            } else if (2 * p < a.n) {  // the record no pair holds: never read past record n - 1
-                const uint2 r = a.dw[2 * p];
-                v[k].x = r.x;
-                v[k].y = r.y;
-                if (kOut) {
-                    lo2[k] = a.lo[2 * p];
-                    hi2[k] = a.hi[hi_pos(2 * p)];
-                }
-            }
-        }
+        PairLoad<kOut, T, U> l;
+        l.load(a.s, base, a.n, tid);
 #pragma unroll
         for (uint32_t k = 0; k < U; ++k) {
-            const uint64_t p = base + k * T + tid;
-            uint32_t s0 = 0, s1 = 0;
-            if (kOut) {
-                s0 = code_src(lo2[k] & 0xFFFFu, hi2[k] & 0xFFu);
-                s1 = code_src(lo2[k] >> 16, (hi2[k] >> 8) & 0xFFu);
-            }
             Item o0, i0, o1, i1;
-            items<kOut, kIn>(a, 2 * p < a.n, s0, v[k].x, v[k].y, t, o0, i0);
-            items<kOut, kIn>(a, 2 * p + 1 < a.n, s1, v[k].z, v[k].w, t, o1, i1);
+            items<kOut, kIn>(a, l.valid0(k), l.src0(k), l.v[k].x, l.v[k].y, t, o0, i0);
+            items<kOut, kIn>(a, l.valid1(k), l.src1(k), l.v[k].z, l.v[k].w, t, o1, i1);
             if (kOut) scatter<kWide, 0>(a, lds, lane, o0, o1);
             if (kIn) scatter<kWide, 1>(a, lds, lane, i0, i1);
         }
@@ -263,15 +227,13 @@ __global__ __launch_bounds__(kDegreeThreads) void k_degree(DegreeArgs a, uint32_
     }
 
     // words 1..5; a strength plane that is not asked leaves its skipped word 0
-    const uint32_t h[5] = {wave_add(a.header ? t.tomb : 0u), wave_add(t.n[0]), wave_add(t.n[1]),
-                           wave_add((a.what & ABNN_DEG_OUT_W) ? t.skip[0] : 0u),
-                           wave_add((a.what & ABNN_DEG_IN_W) ? t.skip[1] : 0u)};
-    if (lane == 0)
-        for (uint32_t j = 0; j < 5; ++j) lds[(tid >> 6) * 8 + j] = h[j];
-    __syncthreads();
-    if (tid < 5) {
+    const uint32_t h[kDegreeHead] = {wave_add(a.header ? t.tomb : 0u), wave_add(t.n[0]), wave_add(t.n[1]),
+                                     wave_add((a.what & ABNN_DEG_OUT_W) ? t.skip[0] : 0u),
+                                     wave_add((a.what & ABNN_DEG_IN_W) ? t.skip[1] : 0u)};
+    wave_words_to_lds(lds, h, tid);
+    if (tid < kDegreeHead) {
         unsigned long long s = 0;
-        for (uint32_t w = 0; w < T / 64; ++w) s += lds[w * 8 + tid];
+        for (uint32_t w = 0; w < T / 64; ++w) s += lds[w * kDegreeHead + tid];
         if (s) atomicAdd(a.out + 1 + tid, s);
     }
     if (a.header && blockIdx.x == 0 && tid == 0) a.out[0] = a.n;  // no other thread touches word 0
@@ -290,7 +252,7 @@ uint32_t plane_bytes(uint32_t what, uint32_t m)
 
 hipError_t launch_one(DegreeArgs a, bool wide, uint32_t cus, hipStream_t s)
 {
-    constexpr uint32_t kScratch = (kDegreeThreads / 64) * 8;  // words for the header sums
+    constexpr uint32_t kScratch = (kDegreeThreads / 64) * kDegreeHead;  // words for the header sums
     uint32_t lds_words = kScratch;
     if (!wide) {
         // 64-bit strengths first (8-byte aligned), then the u32 degrees
@@ -301,16 +263,9 @@ hipError_t launch_one(DegreeArgs a, bool wide, uint32_t cus, hipStream_t s)
         if (a.what & ABNN_DEG_IN) a.l_deg[1] = off, off += a.m;
         lds_words = std::max(off, kScratch);
     }
-    // grid from the CU count: as many workgroups per CU as their planes leave
-    // room for (160 KiB of LDS per CU), at most 4 (32 waves)
-    const uint32_t per_cu = std::min<uint32_t>(4u, (160u * 1024u) / (lds_words * 4u));
-    const uint64_t per_iter = 2ull * kDegreeThreads * kDegreeUnroll;  // records per workgroup iteration
-    const uint64_t iters = (a.n + per_iter - 1) / per_iter;
-    uint64_t grid = std::min<uint64_t>((uint64_t)std::max(1u, cus) * per_cu, iters);
-    const uint64_t max_iters = kDegreeMaxPerWg / per_iter;  // u32 LDS degrees
-    if ((iters + grid - 1) / grid > max_iters) grid = (iters + max_iters - 1) / max_iters;
+    const uint32_t grid = scan_grid(a.n, 2ull * kDegreeThreads * kDegreeUnroll, lds_words, cus, kScanMaxPerWg);
     const bool o = a.what & (ABNN_DEG_OUT | ABNN_DEG_OUT_W), i = a.what & (ABNN_DEG_IN | ABNN_DEG_IN_W);
-    const dim3 g((uint32_t)grid), b(kDegreeThreads);
+    const dim3 g(grid), b(kDegreeThreads);
     const uint32_t bytes = lds_words * 4;
 #define ABNN_DEGREE_LAUNCH(O, I)                                                               \
     do {                                                                                       \
@@ -339,10 +294,7 @@ hipError_t launch_degree(const SynArrays& syn, uint64_t n, const abnn_degree_con
     hipError_t e = hipMemsetAsync(out_dev, 0, words * sizeof(uint64_t), s);
     if (e != hipSuccess || n == 0) return e;
     DegreeArgs a{};
-    a.dw4 = reinterpret_cast<const u32x4*>(syn.dw);
-    a.dw = syn.dw;
-    a.lo = syn.lo;
-    a.hi = syn.hi;
+    a.s = record_stream(syn);
     a.out = reinterpret_cast<unsigned long long*>(out_dev);
     a.n = n;
     a.first = cfg.count ? cfg.first : 0u;

@@ -4,10 +4,10 @@
 // assumption), so an edit may run beside other streams' kernels.
 //
 //   k_edit<kSrc, kOp> : a persistent grid-stride stream over tiles of kEditTile
-//       consecutive records, loaded as k_select_count loads them (16 B = two
-//       {dst, w} records per lane, kEditUnroll loads in flight, non-temporal;
-//       the src streams only in the kSrc instantiation: a src range or
-//       SCALE_SRC).  A lane applies the rule of edit.h to its two records and
+//       consecutive records; the stream is scan.h's (kEditUnroll loads in
+//       flight; kSrc: a src range or SCALE_SRC).  The kernel writes through the
+//       arrays it streams.  A lane applies the rule of edit.h to its two
+//       records and
 //       stores only what CHANGED: w alone (4 B), or the whole 16-B pair when
 //       both records changed.  A kill stores the record's {dst, w} (8 B; 16 B
 //       for both of a pair) and its own src code: the lo halfword, the hi byte
@@ -21,6 +21,7 @@
 // Every count is an integer and every stored value a function of the record
 // and its index alone, so the result does not depend on the grid or on timing.
 #include "edit.h"
+#include "scan.h"
 
 #include <algorithm>
 
@@ -36,14 +37,8 @@ static_assert(kEditTile == (uint32_t)kCompactChunk, "a tile's kills are one entr
 constexpr uint32_t kEditWaves = kEditThreads / 64;
 constexpr int kFactorThreads = 256;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 struct EditArgs {
-    u32x4* dw4;  // the {dst, w} stream, two records per element
-    uint2* dw;
-    uint16_t* lo;
-    uint8_t* hi;
-    uint32_t* src32;  // random mode only
+    SynArrays syn;   // read as record_stream(syn), written in place; src32 in random mode only
     uint32_t* dead;   // the structural update's tally, or null
     const float* plane;
     unsigned long long* out;
@@ -66,9 +61,9 @@ __device__ __forceinline__ void put(bool nt, T* p, T v)
 __device__ __forceinline__ void kill_src(const EditArgs& a, uint64_t i)
 {
     const uint32_t c = src_code(kSrcNone);
-    a.lo[i] = (uint16_t)c;
-    a.hi[hi_pos(i)] = (uint8_t)(c >> 16);
-    if (a.src32) a.src32[i] = kSrcNone;
+    a.syn.lo[i] = (uint16_t)c;
+    a.syn.hi[hi_pos(i)] = (uint8_t)(c >> 16);
+    if (a.syn.src32) a.syn.src32[i] = kSrcNone;
 }
 
 struct Counts {
@@ -102,65 +97,42 @@ __device__ __forceinline__ bool edit_one(const EditArgs& a, uint32_t src, uint32
     return changed;
 }
 
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
 template <bool kSrc, uint32_t kOp>
 __global__ __launch_bounds__(kEditThreads) void k_edit(EditArgs a)
 {
     constexpr uint32_t U = kEditUnroll;
     constexpr bool kKill = kOp == ABNN_EDIT_KILL;
     __shared__ uint32_t wave_kills[2][kEditWaves];
-    __shared__ uint32_t wave_counts[5][kEditWaves];
+    __shared__ uint32_t wave_counts[kEditWaves * 5];
     const uint32_t tid = threadIdx.x;
-    const uint64_t n_pairs = a.n >> 1;
+    const RecordStream rs = record_stream(a.syn);
     const bool nt = a.nt != 0;
     Counts c;
     uint32_t parity = 0;
     for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x, parity ^= 1) {
         const uint64_t first_pair = tile * (kEditTile / 2);
-        // every load before the first use
-        u32x4 v[U];
-        uint32_t lo2[U], hi2[U];
-#pragma unroll
-        for (uint32_t k = 0; k < U; ++k) {
-            const uint64_t p = first_pair + k * kEditThreads + tid;
-            v[k] = u32x4{kEditTomb, 0u, kEditTomb, 0u};  // past the end: a tombstone, no match
-            lo2[k] = hi2[k] = 0;
-            if (p < n_pairs) {
-                v[k] = __builtin_nontemporal_load(a.dw4 + p);
-                if (kSrc) {
-                    lo2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.lo) + p);
-                    hi2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(a.hi) + p);
-                }
-            }
-        }
+        PairLoad<kSrc, kEditThreads, U, false> l;  // an absent record: a tombstone, no match
+        l.load(rs, first_pair, a.n, tid);
         uint32_t tile_kills = 0;
 #pragma unroll
         for (uint32_t k = 0; k < U; ++k) {
-            const uint64_t p = first_pair + k * kEditThreads + tid;
-            const bool in = p < n_pairs;
-            c.tomb += in ? (v[k].x == kEditTomb) + (v[k].z == kEditTomb) : 0u;
-            const uint32_t s0 = kSrc ? code_src(lo2[k] & 0xFFFFu, hi2[k] & 0xFFu) : 0u;
-            const uint32_t s1 = kSrc ? code_src(lo2[k] >> 16, (hi2[k] >> 8) & 0xFFu) : 0u;
-            uint32_t w0 = v[k].y, w1 = v[k].w;
+            const uint64_t p = l.pair(k);
+            c.tomb += l.whole(k) ? (l.v[k].x == kEditTomb) + (l.v[k].z == kEditTomb) : 0u;
+            uint32_t w0 = l.v[k].y, w1 = l.v[k].w;
             const uint64_t i = p << 1;
-            const bool st0 = edit_one<kSrc, kOp>(a, s0, v[k].x, w0, i, c);
-            const bool st1 = edit_one<kSrc, kOp>(a, s1, v[k].z, w1, i + 1, c);
-            if (!(st0 || st1)) continue;  // a store only where a record changed (p < n_pairs: it matched)
-            const uint32_t d0 = kKill && st0 ? kEditTomb : v[k].x, d1 = kKill && st1 ? kEditTomb : v[k].z;
+            const bool st0 = edit_one<kSrc, kOp>(a, l.src0(k), l.v[k].x, w0, i, c);
+            const bool st1 = edit_one<kSrc, kOp>(a, l.src1(k), l.v[k].z, w1, i + 1, c);
+            if (!(st0 || st1)) continue;  // a store only where a record changed (it exists: it matched)
+            const uint32_t d0 = kKill && st0 ? kEditTomb : l.v[k].x, d1 = kKill && st1 ? kEditTomb : l.v[k].z;
             if (st0 && st1) {
-                put(nt, a.dw4 + p, u32x4{d0, w0, d1, w1});
+                put(nt, reinterpret_cast<u32x4*>(a.syn.dw) + p, u32x4{d0, w0, d1, w1});
             } else if (kKill) {
                 const uint64_t j = st0 ? i : i + 1;
-                put(nt, reinterpret_cast<unsigned long long*>(a.dw + j),
+                put(nt, reinterpret_cast<unsigned long long*>(a.syn.dw + j),
                     (unsigned long long)(st0 ? w0 : w1) << 32 | 0xFFFFFFFFull);  // {dst, w} as one 8-B store
             } else {
                 const uint64_t j = st0 ? i : i + 1;
-                put(nt, reinterpret_cast<uint32_t*>(a.dw + j) + 1, st0 ? w0 : w1);
+                put(nt, reinterpret_cast<uint32_t*>(a.syn.dw + j) + 1, st0 ? w0 : w1);
             }
             if (kKill) {
                 if (st0) kill_src(a, i);
@@ -169,9 +141,9 @@ __global__ __launch_bounds__(kEditThreads) void k_edit(EditArgs a)
             }
         }
         if (kKill && a.dead) {  // uniform: the tile's kills into the tally with one atomic
-            tile_kills = wave_add(tile_kills);
-            if ((tid & 63) == 0) wave_kills[parity][tid >> 6] = tile_kills;
-            __syncthreads();  // one per tile: the parity keeps the next tile's writes off this one's reads
+            const uint32_t h[1] = {wave_add(tile_kills)};
+            // one barrier per tile: the parity keeps the next tile's writes off this one's reads
+            wave_words_to_lds(wave_kills[parity], h, tid);
             if (tid == 0) {
                 uint32_t s = 0;
                 for (uint32_t w = 0; w < kEditWaves; ++w) s += wave_kills[parity][w];
@@ -179,29 +151,27 @@ __global__ __launch_bounds__(kEditThreads) void k_edit(EditArgs a)
             }
         }
     }
-    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {  // the record no pair holds
+    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {
+        const OddRecord r = odd_record<kSrc>(rs, a.n);
         const uint64_t i = a.n - 1;
-        const uint2 r = a.dw[i];
-        c.tomb += r.x == kEditTomb;
-        uint32_t w = r.y;
-        if (edit_one<kSrc, kOp>(a, kSrc ? code_src(a.lo[i], a.hi[hi_pos(i)]) : 0u, r.x, w, i, c)) {
+        c.tomb += r.dst == kEditTomb;
+        uint32_t w = r.w;
+        if (edit_one<kSrc, kOp>(a, r.src, r.dst, w, i, c)) {
             if (kKill) {
-                put(nt, reinterpret_cast<unsigned long long*>(a.dw + i), (unsigned long long)w << 32 | 0xFFFFFFFFull);
+                put(nt, reinterpret_cast<unsigned long long*>(a.syn.dw + i), (unsigned long long)w << 32 | 0xFFFFFFFFull);
                 kill_src(a, i);
                 if (a.dead) atomicAdd(a.dead + i / kCompactChunk, 1u);
             } else {
-                put(nt, reinterpret_cast<uint32_t*>(a.dw + i) + 1, w);
+                put(nt, reinterpret_cast<uint32_t*>(a.syn.dw + i) + 1, w);
             }
         }
     }
     const uint32_t sums[5] = {wave_add(c.tomb), wave_add(c.matched), wave_add(c.changed), wave_add(c.killed),
                               wave_add(c.bad)};
-    if ((tid & 63) == 0)
-        for (uint32_t q = 0; q < 5; ++q) wave_counts[q][tid >> 6] = sums[q];
-    __syncthreads();
+    wave_words_to_lds(wave_counts, sums, tid);
     if (tid < 5) {
         unsigned long long s = 0;
-        for (uint32_t w = 0; w < kEditWaves; ++w) s += wave_counts[tid][w];
+        for (uint32_t w = 0; w < kEditWaves; ++w) s += wave_counts[w * 5 + tid];
         if (s) atomicAdd(a.out + 1 + tid, s);  // words 1..5
     }
     if (blockIdx.x == 0 && tid == 0) atomicAdd(a.out, (unsigned long long)a.n);  // zeroed before the launch
@@ -236,11 +206,7 @@ hipError_t launch_edit(const SynArrays& syn, uint64_t n, const EditRule& rule, c
     hipError_t e = hipMemsetAsync(out_dev, 0, ABNN_EDIT_HEADER_WORDS * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
     EditArgs a{};
-    a.dw4 = reinterpret_cast<u32x4*>(syn.dw);
-    a.dw = syn.dw;
-    a.lo = syn.lo;
-    a.hi = syn.hi;
-    a.src32 = syn.src32;
+    a.syn = syn;
     a.dead = dead;
     a.plane = plane_dev;
     a.out = reinterpret_cast<unsigned long long*>(out_dev);

@@ -24,6 +24,7 @@
 //       be: a shard whose offset is odd or a block boundary inside a quad only
 //       takes the boundary path.
 #include "graph.h"
+#include "scan.h"
 
 #include <algorithm>
 
@@ -32,7 +33,6 @@
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 template <bool kNT, typename T>

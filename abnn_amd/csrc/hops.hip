@@ -21,10 +21,10 @@
 //         load of an iteration issued before its first use; decodes the src,
 //         tests its frontier bit (the eight bitmap gathers issued together),
 //         and only for a hit gathers dw[k].
-//       reverse: streams {dst, w} as 16-B pairs (k_degree's stream), tests the
+//       reverse: the stream is scan.h's, without the src streams; tests the
 //         bit of dst, and only for a hit reads lo[k] and hi[k].
-//       The records that no whole 16-B load holds (n_syn % 8, n_syn % 2) are
-//       read one at a time by one thread: nothing is read past record n_syn - 1.
+//       The records that no whole forward load holds (n_syn % 8) are read one
+//       at a time by one thread: nothing is read past record n_syn - 1.
 //       A hit that is live, in bounds and inside the weight interval issues
 //       atomicMin(plane[v], h + 1) (agent scope, relaxed, no return).  The plain
 //       read of plane[v] before it only skips the atomic for a neuron that is
@@ -33,17 +33,18 @@
 //       on the atomic alone.
 //   k_hops_close     : one workgroup, header words 0..4 from the levels.
 #include "hops.h"
+#include "scan.h"
 
 #pragma clang fp contract(off)
 
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned long long u64;
 
 constexpr uint32_t kUnreached = ABNN_HOPS_UNREACHED;
+static_assert(kUnreached == kAbsentDst, "the reverse pass: an absent record is one whose dst is no neuron");
 
 struct HopsArgs {
     const uint16_t* lo;
@@ -60,12 +61,6 @@ __device__ __forceinline__ u64* levels_of(u64* out) { return out + ABNN_HOPS_HEA
 __device__ __forceinline__ uint32_t* plane_of(u64* out, uint32_t H)
 {
     return reinterpret_cast<uint32_t*>(out + ABNN_HOPS_HEADER_WORDS + H + 1);
-}
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
 }
 
 __global__ __launch_bounds__(kHopsFrontierThreads) void k_hops_begin(u64* out, uint32_t H, uint32_t n_nrn, uint32_t first,
@@ -256,33 +251,24 @@ __global__ __launch_bounds__(kHopsThreads) void k_hops_expand(HopsArgs a)
         }
     } else {
         constexpr uint32_t U = kHopsRevUnroll;
-        const u32x4* dw4 = reinterpret_cast<const u32x4*>(a.dw);
-        const uint64_t n_pairs = a.n >> 1;  // whole 16-B pairs
+        const RecordStream rs{reinterpret_cast<const u32x4*>(a.dw), a.dw, a.lo, a.hi};
+        const uint64_t n_pairs = scan_pairs(a.n);
         const uint64_t stride = (uint64_t)gridDim.x * (T * U);
         for (uint64_t base = (uint64_t)blockIdx.x * (T * U); base < n_pairs; base += stride) {
-            u32x4 v[U];
-#pragma unroll
-            for (uint32_t k = 0; k < U; ++k) {
-                const uint64_t p = base + k * T + tid;
-                v[k] = u32x4{kUnreached, 0u, kUnreached, 0u};  // absent records: a dst above N_NRN
-                if (p < n_pairs) v[k] = __builtin_nontemporal_load(dw4 + p);
-            }
+            PairLoad<false, T, U> l;  // an absent record: a dst above N_NRN
+            l.load(rs, base, a.n, tid);
             uint32_t w0[U], w1[U];
 #pragma unroll
             for (uint32_t k = 0; k < U; ++k) {
-                w0[k] = frontier_word(a, fold, use_fold, v[k].x);
-                w1[k] = frontier_word(a, fold, use_fold, v[k].z);
+                w0[k] = frontier_word(a, fold, use_fold, l.v[k].x);
+                w1[k] = frontier_word(a, fold, use_fold, l.v[k].z);
             }
 #pragma unroll
             for (uint32_t k = 0; k < U; ++k) {
-                const uint64_t p = base + k * T + tid;
-                reverse_record<kWeight>(a, plane, 2 * p, v[k].x, v[k].y, w0[k]);
-                reverse_record<kWeight>(a, plane, 2 * p + 1, v[k].z, v[k].w, w1[k]);
+                const uint64_t p = l.pair(k);
+                reverse_record<kWeight>(a, plane, 2 * p, l.v[k].x, l.v[k].y, w0[k]);
+                reverse_record<kWeight>(a, plane, 2 * p + 1, l.v[k].z, l.v[k].w, w1[k]);
             }
-        }
-        if ((a.n & 1u) && blockIdx.x == 0 && tid == 0) {  // the record no pair holds
-            const uint2 r = a.dw[a.n - 1];
-            reverse_record<kWeight>(a, plane, a.n - 1, r.x, r.y, frontier_word(a, fold, use_fold, r.x));
         }
     }
 }
@@ -358,7 +344,7 @@ hipError_t launch_hops_step(const SynArrays& syn, uint64_t n, const abnn_hops_co
     a.w_hi = cfg.w_hi;
     const bool rev = cfg.flags & ABNN_HOPS_REVERSE, wt = cfg.flags & ABNN_HOPS_WEIGHT;
     // records per workgroup iteration; 4 workgroups (32 waves) per CU, as the census.  At least one
-    // workgroup: its first thread takes the records that no whole 16-B load holds.
+    // workgroup: forward, its first thread takes the records that no whole load holds.
     const uint64_t per_iter = rev ? 2ull * kHopsThreads * kHopsRevUnroll : 8ull * kHopsThreads * kHopsFwdUnroll;
     const uint64_t iters = (n + per_iter - 1) / per_iter;
     const dim3 g((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4ull * cus, iters))), b(kHopsThreads);

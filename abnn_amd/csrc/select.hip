@@ -5,9 +5,8 @@
 // residency assumption), so a select may run beside other streams' kernels.
 //
 //   k_select_count<kSrc> : a persistent grid-stride stream over tiles of
-//       kSelectTile consecutive records, loaded as k_census loads them (16 B =
-//       two {dst, w} records per lane, kSelectUnroll loads in flight,
-//       non-temporal; the src streams only in the kSrc instantiation).  A wave
+//       kSelectTile consecutive records; the stream is scan.h's (kSelectUnroll
+//       loads in flight; kSrc: a src range is set).  A wave
 //       adds its matches of a tile to the tile's u32 count (zeroed before the
 //       launch; a wave without a match adds nothing), the workgroup its
 //       tombstones to header word 1 with one atomic.
@@ -28,6 +27,7 @@
 // 16-B pair -- the index order.  Every count is an integer, every position
 // offset + rank, so the result does not depend on the grid or on timing.
 #include "select.h"
+#include "scan.h"
 
 #include <algorithm>
 
@@ -36,16 +36,12 @@
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 // the record plane starts 8 * (8 + capacity) bytes into the result: 8-byte aligned
 typedef uint32_t u32x4a8 __attribute__((ext_vector_type(4), aligned(8)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 struct SelectArgs {
-    const u32x4* dw4;  // the {dst, w} stream, two records per element
-    const uint2* dw;
-    const uint16_t* lo;
-    const uint8_t* hi;
+    RecordStream s;
     uint32_t* counts;             // [select_count_words(n)] matches per tile
     unsigned long long* offsets;  // [tiles] matches before the tile
     unsigned long long* out;
@@ -61,7 +57,7 @@ struct SelectArgs {
 template <bool kSrc>
 __device__ __forceinline__ bool match(const SelectArgs& a, uint32_t src, uint32_t dst, uint32_t wbits)
 {
-    if (dst == 0xFFFFFFFFu) return false;
+    if (dst == kAbsentDst) return false;  // a tombstone, or no record
     const bool D = dst - a.dst_first < a.dst_span;
     const bool S = kSrc ? src - a.src_first < a.src_span : a.any == 0;
     bool m = a.any ? (S || D) : (S && D);
@@ -72,37 +68,8 @@ __device__ __forceinline__ bool match(const SelectArgs& a, uint32_t src, uint32_
     return m;
 }
 
-// One tile's loads: every load before the first use.
 template <bool kSrc>
-struct TileLoad {
-    u32x4 v[kSelectUnroll];
-    uint32_t lo2[kSelectUnroll], hi2[kSelectUnroll];
-
-    __device__ __forceinline__ void load(const SelectArgs& a, uint64_t first_pair, uint64_t n_pairs, uint32_t tid)
-    {
-#pragma unroll
-        for (uint32_t k = 0; k < (uint32_t)kSelectUnroll; ++k) {
-            const uint64_t p = first_pair + k * kSelectThreads + tid;
-            v[k] = u32x4{0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0u};
-            lo2[k] = hi2[k] = 0;
-            if (p < n_pairs) {
-                v[k] = __builtin_nontemporal_load(a.dw4 + p);
-                if (kSrc) {
-                    lo2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(a.lo) + p);
-                    hi2[k] = __builtin_nontemporal_load(reinterpret_cast<const uint16_t*>(a.hi) + p);
-                }
-            }
-        }
-    }
-    __device__ __forceinline__ uint32_t src0(uint32_t k) const { return kSrc ? code_src(lo2[k] & 0xFFFFu, hi2[k] & 0xFFu) : 0u; }
-    __device__ __forceinline__ uint32_t src1(uint32_t k) const { return kSrc ? code_src(lo2[k] >> 16, (hi2[k] >> 8) & 0xFFu) : 0u; }
-};
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
+using Tile = PairLoad<kSrc, kSelectThreads, kSelectUnroll, false>;  // one tile's loads; the odd record after them
 
 // inclusive prefix sum over the 64 lanes of a wave
 __device__ __forceinline__ uint32_t wave_scan(uint32_t v, uint32_t lane)
@@ -120,32 +87,28 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_count(SelectArgs a)
     __shared__ uint32_t wave_tomb[kSelectThreads / 64];
     constexpr uint32_t U = kSelectUnroll;
     const uint32_t tid = threadIdx.x;
-    const uint64_t n_pairs = a.n >> 1;
     uint32_t tomb = 0;
     for (uint64_t tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
         const uint64_t first_pair = tile * (kSelectTile / 2);
-        TileLoad<kSrc> t;
-        t.load(a, first_pair, n_pairs, tid);
+        Tile<kSrc> t;
+        t.load(a.s, first_pair, a.n, tid);
         uint32_t wave_matches = 0;  // wave-uniform
 #pragma unroll
         for (uint32_t k = 0; k < U; ++k) {
-            const bool in = first_pair + k * kSelectThreads + tid < n_pairs;
-            tomb += in ? (t.v[k].x == 0xFFFFFFFFu) + (t.v[k].z == 0xFFFFFFFFu) : 0u;
-            const bool m0 = match<kSrc>(a, t.src0(k), t.v[k].x, t.v[k].y);  // past the end: a tombstone, no match
+            tomb += t.whole(k) ? (t.v[k].x == kAbsentDst) + (t.v[k].z == kAbsentDst) : 0u;
+            const bool m0 = match<kSrc>(a, t.src0(k), t.v[k].x, t.v[k].y);
             const bool m1 = match<kSrc>(a, t.src1(k), t.v[k].z, t.v[k].w);
             wave_matches += __popcll(__ballot(m0)) + __popcll(__ballot(m1));
         }
         if ((tid & 63) == 0 && wave_matches) atomicAdd(a.counts + tile, wave_matches);
     }
-    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {  // the record no pair holds: the last of the last tile
-        const uint64_t i = a.n - 1;
-        const uint2 r = a.dw[i];
-        tomb += r.x == 0xFFFFFFFFu;
-        if (match<kSrc>(a, kSrc ? code_src(a.lo[i], a.hi[hi_pos(i)]) : 0u, r.x, r.y)) atomicAdd(a.counts + (a.tiles - 1), 1u);
+    if ((a.n & 1) && blockIdx.x == 0 && tid == 0) {  // the last of the last tile
+        const OddRecord r = odd_record<kSrc>(a.s, a.n);
+        tomb += r.dst == kAbsentDst;
+        if (match<kSrc>(a, r.src, r.dst, r.w)) atomicAdd(a.counts + (a.tiles - 1), 1u);
     }
-    tomb = wave_add(tomb);
-    if ((tid & 63) == 0) wave_tomb[tid >> 6] = tomb;
-    __syncthreads();
+    const uint32_t h[1] = {wave_add(tomb)};
+    wave_words_to_lds(wave_tomb, h, tid);
     if (tid == 0) {
         unsigned long long s = 0;
         for (uint32_t w = 0; w < kSelectThreads / 64; ++w) s += wave_tomb[w];
@@ -231,7 +194,7 @@ __device__ __forceinline__ void emit_one(const SelectArgs& a, u32x4a8* rec, unsi
                                          uint32_t dst, uint32_t wbits)
 {
     if (pos >= a.capacity) return;
-    if (!kSrc) src = code_src(a.lo[i], a.hi[hi_pos(i)]);
+    if (!kSrc) src = code_src(a.s.lo[i], a.s.hi[hi_pos(i)]);
     a.out[ABNN_SELECT_HEADER_WORDS + pos] = a.syn_offset + i;
     rec[pos] = u32x4a8{src, dst, wbits, 0u};
 }
@@ -245,7 +208,6 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_emit(SelectArgs a)
     __shared__ uint32_t list[kSelectEmitChunk];
     __shared__ uint32_t n_list;
     const uint32_t tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint64_t n_pairs = a.n >> 1;
     u32x4a8* rec = reinterpret_cast<u32x4a8*>(a.out + ABNN_SELECT_HEADER_WORDS + a.capacity);
     uint32_t parity = 0;
     // workgroup b looks at tiles b, b + G, b + 2G, ... (G workgroups), 64 of
@@ -264,8 +226,8 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_emit(SelectArgs a)
             const uint64_t tile = (chunk + list[q]) * G + blockIdx.x;
             const unsigned long long offset = a.offsets[tile];
             const uint64_t first_pair = tile * (kSelectTile / 2);
-            TileLoad<kSrc> t;
-            t.load(a, first_pair, n_pairs, tid);
+            Tile<kSrc> t;
+            t.load(a.s, first_pair, a.n, tid);
             unsigned long long b0[U], b1[U];
             bool m0[U], m1[U];
 #pragma unroll
@@ -286,16 +248,13 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_emit(SelectArgs a)
                 const uint32_t e = k * W + wave;
                 const uint32_t groups = e ? __shfl(before, e - 1) : 0u;
                 const uint32_t r0 = groups + __popcll(b0[k] & below) + __popcll(b1[k] & below);
-                const uint64_t i = (first_pair + k * kSelectThreads + tid) << 1;
+                const uint64_t i = t.pair(k) << 1;
                 if (m0[k]) emit_one<kSrc>(a, rec, offset + r0, i, t.src0(k), t.v[k].x, t.v[k].y);
                 if (m1[k]) emit_one<kSrc>(a, rec, offset + r0 + (m0[k] ? 1u : 0u), i + 1, t.src1(k), t.v[k].z, t.v[k].w);
             }
-            if ((a.n & 1) && tile == a.tiles - 1 && tid == 0) {  // the record no pair holds: after every pair of the tile
-                const uint64_t i = a.n - 1;
-                const uint2 r = a.dw[i];
-                const uint32_t src = kSrc ? code_src(a.lo[i], a.hi[hi_pos(i)]) : 0u;
-                if (match<kSrc>(a, src, r.x, r.y))
-                    emit_one<kSrc>(a, rec, offset + in_pairs, i, src, r.x, r.y);
+            if ((a.n & 1) && tile == a.tiles - 1 && tid == 0) {  // after every pair of the tile
+                const OddRecord r = odd_record<kSrc>(a.s, a.n);
+                if (match<kSrc>(a, r.src, r.dst, r.w)) emit_one<kSrc>(a, rec, offset + in_pairs, a.n - 1, r.src, r.dst, r.w);
             }
         }
         __syncthreads();  // list and n_list are rewritten by the next chunk
@@ -311,10 +270,7 @@ hipError_t launch_select(const SynArrays& syn, uint64_t n, uint64_t syn_offset, 
     hipError_t e = hipMemsetAsync(out_dev, 0, ABNN_SELECT_HEADER_WORDS * sizeof(uint64_t), s);
     if (e != hipSuccess) return e;
     SelectArgs a{};
-    a.dw4 = reinterpret_cast<const u32x4*>(syn.dw);
-    a.dw = syn.dw;
-    a.lo = syn.lo;
-    a.hi = syn.hi;
+    a.s = record_stream(syn);
     a.counts = scratch.counts;
     a.offsets = reinterpret_cast<unsigned long long*>(scratch.offsets);
     a.out = reinterpret_cast<unsigned long long*>(out_dev);

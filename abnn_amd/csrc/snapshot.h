@@ -185,8 +185,6 @@ constexpr int kDiffThreads = 512;  // 8 waves per workgroup
 // 16-B loads in flight per lane and side.  Measured at config 3: 2 -> 3.55 ms (80 VGPRs, three workgroups per
 // CU), 1 -> 3.80 ms, 4 -> 5.33 ms (144 VGPRs leave one workgroup per CU)
 constexpr int kDiffUnroll = 2;
-// a workgroup's LDS counters are u32: no workgroup scans more records than this
-constexpr uint64_t kDiffMaxPerWg = 1ull << 31;
 
 // Zeroes out_dev (diff_words u64) and fills it with the diff of records
 // [0, min(n_then, n_now)) of `then` and `now` (lo, hi and dw; src32 is not

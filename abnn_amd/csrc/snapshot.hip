@@ -5,23 +5,21 @@
 // every result word is an integer sum or maximum, so the result depends on
 // neither the grid nor the order; abnn_amd/snapshot.py restates it in numpy.
 //
-//   k_diff : as k_census (census.hip).  Each lane loads 16 B = two {dst, w}
-//       records from each side, and the two src streams of each side (4 B of lo
-//       words, 2 B of hi bytes per pair and side): 22 B per record, every load
-//       non-temporal (each side is read once), kDiffUnroll pairs in flight.
-//       The class counts, net / abs and the maximum stay in registers; bins go
-//       to a workgroup histogram in LDS kept in `copies` interleaved images
-//       (census_copies' rule: hist[bin * copies + (lane & (copies - 1))]):
-//       almost every d of a learning run falls into the one or two bins around
-//       0, the census's constant-weight case.  The histogram is flushed once
-//       per workgroup with global u64 atomics (zero bins skipped), then the
-//       header: the waves reduce their counts, one atomic per word and
+//   k_diff : as k_census (census.hip): scan.h's RecordStream once per side,
+//       read by the kernel's own loop with both src streams (22 B per record,
+//       kDiffUnroll pairs per lane and iteration), the odd last record by
+//       odd_record().  The class counts, net / abs and the maximum stay in registers;
+//       bins go to scan.h's bank-spread histogram in LDS: almost every d of a
+//       learning run falls into the one or two bins around 0, the census's
+//       constant-weight case.  The histogram is flushed once per workgroup
+//       with global u64 atomics, then the header: one atomic per word and
 //       workgroup.  Workgroups are independent: no look-back, no ticket, no
 //       residency assumption.
 //   k_diff_finish : one thread, in stream order after it: words 0 .. 4.
 //   k_src32_sync : the random-mode src mirror from the two src streams, after a
 //       restore copied the streams over.
 #include "snapshot.h"
+#include "scan.h"
 
 #include <algorithm>
 
@@ -30,30 +28,10 @@
 namespace abnn {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr uint32_t kDiffLdsWords = 16384;  // 64 KiB of u32 counters per workgroup
-constexpr uint32_t kDiffMaxCopies = 32;    // histogram copies, chosen by lane & (copies - 1)
-constexpr uint32_t kDiffHead = 18;         // header sums per wave: words 5 .. 18, 21, net, abs, the maximum
-
-// Histogram copies for `bins` bins: the most (a power of two, at most one per
-// LDS bank) that fit the workgroup's counters.  4096 bins -> 4, <= 512 -> 32.
-uint32_t diff_copies(uint32_t bins)
-{
-    uint32_t r = kDiffMaxCopies;
-    while (r > 1 && (uint64_t)bins * r > kDiffLdsWords) r >>= 1;
-    return r;
-}
-
-struct DiffSide {
-    const u32x4* dw4;  // the {dst, w} stream, two records per element
-    const uint2* dw;
-    const uint16_t* lo;
-    const uint8_t* hi;
-};
+constexpr uint32_t kDiffHead = 18;  // header sums per wave: words 5 .. 18, 21, net, abs, the maximum
 
 struct DiffArgs {
-    DiffSide a, b;  // then, now
+    RecordStream a, b;  // then, now
     unsigned long long* out;
     uint64_t n;  // records compared: min(n_then, n_now)
     DiffRule rule;
@@ -64,32 +42,7 @@ __device__ __forceinline__ void diff_one(const DiffArgs& g, uint32_t* hist, uint
                                          uint32_t wa, uint32_t sb, uint32_t db, uint32_t wb, DiffTally<uint32_t>& t)
 {
     const uint32_t bin = diff_record(g.rule, sa, da, wa, sb, db, wb, t);
-    if (bin != kDiffNoBin)
-        __hip_atomic_fetch_add(&hist[bin * g.copies + copy], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-__device__ __forceinline__ uint32_t wave_add(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_max(uint32_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) {
-        const uint32_t o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-__device__ __forceinline__ uint64_t wave_add64(uint64_t v)
-{
-    for (int m = 32; m > 0; m >>= 1) {
-        const uint32_t lo = __shfl_xor((uint32_t)v, m), hi = __shfl_xor((uint32_t)(v >> 32), m);
-        v += (uint64_t)hi << 32 | lo;
-    }
-    return v;
+    if (bin != kDiffNoBin) hist_add(hist, g.copies, copy, bin);
 }
 
 __global__ __launch_bounds__(kDiffThreads) void k_diff(DiffArgs g)
@@ -103,13 +56,18 @@ __global__ __launch_bounds__(kDiffThreads) void k_diff(DiffArgs g)
 
     const uint32_t copy = tid & (g.copies - 1);
     DiffTally<uint32_t> t;
-    const uint64_t n_pairs = g.n >> 1;
+    const uint64_t n_pairs = g.n >> 1;  // whole pairs
     const uint64_t stride = (uint64_t)gridDim.x * (T * U);
     for (uint64_t base = (uint64_t)blockIdx.x * (T * U); base < n_pairs; base += stride) {
+        // The loads stay written out here, not PairLoad's, as in k_census and
+        // for its reason: the diff's speed rests on the schedule the compiler
+        // gives this loop (profiles/scan_refactor_ab.txt).  A change of the
+        // record layout must be made here and in k_census (census.hip) as
+        // well as in scan.h.
         u32x4 va[U], vb[U];
         uint32_t la[U], lb[U], ha[U], hb[U];
 #pragma unroll
-        for (uint32_t k = 0; k < U; ++k) {  // every load of the iteration before its first use
+        for (uint32_t k = 0; k < U; ++k) {
             const uint64_t p = base + k * T + tid;
             if (p < n_pairs) {
                 va[k] = __builtin_nontemporal_load(g.a.dw4 + p);
@@ -131,21 +89,13 @@ __global__ __launch_bounds__(kDiffThreads) void k_diff(DiffArgs g)
             }
         }
     }
-    if ((g.n & 1) && blockIdx.x == 0 && tid == 0) {  // the record no pair holds
-        const uint64_t i = g.n - 1;
-        const uint2 ra = g.a.dw[i], rb = g.b.dw[i];
-        diff_one(g, hist, copy, code_src(g.a.lo[i], g.a.hi[hi_pos(i)]), ra.x, ra.y,
-                 code_src(g.b.lo[i], g.b.hi[hi_pos(i)]), rb.x, rb.y, t);
+    if ((g.n & 1) && blockIdx.x == 0 && tid == 0) {
+        const OddRecord ra = odd_record<true>(g.a, g.n), rb = odd_record<true>(g.b, g.n);
+        diff_one(g, hist, copy, ra.src, ra.dst, ra.w, rb.src, rb.dst, rb.w, t);
     }
     __syncthreads();
 
-    // flush: a thread sums the copies of its bins, starting at its own copy so
-    // that the lanes of a wave read different banks
-    for (uint32_t b = tid; b < g.rule.bins; b += T) {
-        uint32_t s = 0;
-        for (uint32_t r = 0; r < g.copies; ++r) s += hist[b * g.copies + ((r + tid) & (g.copies - 1))];
-        if (s) atomicAdd(g.out + ABNN_DIFF_HEADER_WORDS + b, (unsigned long long)s);
-    }
+    hist_flush(hist, g.rule.bins, g.copies, tid, T, g.out + ABNN_DIFF_HEADER_WORDS);
     __syncthreads();  // the histogram is reused for the waves' header sums
 
     // the header: every wave's sums, then one atomic per word and workgroup
@@ -154,14 +104,10 @@ __global__ __launch_bounds__(kDiffThreads) void k_diff(DiffArgs g)
 #pragma unroll
     for (uint32_t j = 0; j < 14; ++j) h[j] = wave_add(t.count[j]);
     h[14] = wave_add(t.not_summable);
-    h[15] = wave_add64((uint64_t)t.net);
-    h[16] = wave_add64(t.abs);
+    h[15] = wave_add((uint64_t)t.net);
+    h[16] = wave_add(t.abs);
     h[17] = wave_max(t.max_bits);
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (uint32_t j = 0; j < kDiffHead; ++j) s_head[(tid >> 6) * kDiffHead + j] = h[j];
-    }
-    __syncthreads();
+    wave_words_to_lds(s_head, h, tid);
     if (tid < kDiffHead) {
         uint64_t s = 0;
         for (uint32_t w = 0; w < T / 64; ++w) {
@@ -195,11 +141,6 @@ __global__ __launch_bounds__(256) void k_src32_sync(SynArrays a, uint64_t n)
         a.src32[i] = code_src(a.lo[i], a.hi[hi_pos(i)]);
 }
 
-DiffSide side(const SynArrays& s)
-{
-    return DiffSide{reinterpret_cast<const u32x4*>(s.dw), s.dw, s.lo, s.hi};
-}
-
 }  // namespace
 
 hipError_t launch_diff(const SynArrays& then, uint64_t n_then, const SynArrays& now, uint64_t n_now,
@@ -212,23 +153,15 @@ hipError_t launch_diff(const SynArrays& then, uint64_t n_then, const SynArrays& 
     const uint64_t n = std::min(n_then, n_now);
     if (n > 0) {
         DiffArgs g{};
-        g.a = side(then);
-        g.b = side(now);
+        g.a = record_stream(then);
+        g.b = record_stream(now);
         g.out = out;
         g.n = n;
         g.rule = rule;
-        g.copies = diff_copies(rule.bins);
+        g.copies = hist_copies(rule.bins);
         const uint32_t lds_words = std::max<uint32_t>(g.rule.bins * g.copies, (kDiffThreads / 64) * 2 * kDiffHead);
-        // grid from the CU count: as many workgroups per CU as their histograms
-        // leave room for (160 KiB of LDS per CU), at most 4 (32 waves)
-        const uint32_t per_cu = std::min<uint32_t>(4u, (160u * 1024u) / (lds_words * 4u));
-        const uint64_t per_iter = 2ull * kDiffThreads * kDiffUnroll;  // records per workgroup iteration
-        const uint64_t iters = (n + per_iter - 1) / per_iter;
-        uint64_t grid = std::min<uint64_t>((uint64_t)std::max(1u, cus) * std::max(1u, per_cu), iters);
-        // u32 LDS counters: no workgroup scans more than kDiffMaxPerWg records
-        const uint64_t max_iters = kDiffMaxPerWg / per_iter;
-        if ((iters + grid - 1) / grid > max_iters) grid = (iters + max_iters - 1) / max_iters;
-        hipLaunchKernelGGL(k_diff, dim3((uint32_t)grid), dim3(kDiffThreads), lds_words * 4, s, g);
+        const uint32_t grid = scan_grid(n, 2ull * kDiffThreads * kDiffUnroll, lds_words, cus, kScanMaxPerWg);
+        hipLaunchKernelGGL(k_diff, dim3(grid), dim3(kDiffThreads), lds_words * 4, s, g);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

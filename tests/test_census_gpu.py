@@ -73,7 +73,9 @@ def _brain(n_syn, **kw):
 
 
 # ---- 1. record-count edges ---------------------------------------------------------------------
-@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000])
+# 4096 records are one workgroup iteration (2 x 512 threads x 4 loads): 4095 .. 4097 cross it with and without
+# the odd last record, 8193 is two iterations and that record
+@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000, 2, 3, 4095, 4096, 4097, 8193])
 def test_record_count_edges(gpu, n_syn):
     planted = set()
     with _brain(n_syn) as b:
@@ -88,6 +90,9 @@ def test_record_count_edges(gpu, n_syn):
                 got = _against_reference(b, bins, 0.0, 1.0, syn=back, what=f"n {n_syn} bins {bins} seed {seed}")
                 assert got["records"] == n_syn and got["selected"] == n_syn and got["tombstones"] == 0
             _against_reference(b, 64, -0.1, 1.1, syn=back, what=f"n {n_syn} wide")
+            # the instance that reads the src streams
+            ranged = _against_reference(b, 64, 0.0, 1.0, src=(0, 500), syn=back, what=f"n {n_syn} src range")
+            assert ranged["selected"] == int((back["src"] < 500).sum())
     assert planted >= set(EDGES.view(np.uint32).tolist())
 
 

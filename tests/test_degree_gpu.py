@@ -85,7 +85,9 @@ def _big_brain():
 
 
 # ---- 1. record-count edges ---------------------------------------------------------------------
-@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000])
+# 4096 records are one workgroup iteration (2 x 512 threads x 4 loads): 4095 .. 4097 cross it with and without
+# the odd last record, 8193 is two iterations and that record
+@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000, 2, 3, 4095, 4096, 4097, 8193])
 def test_record_count_edges(gpu, n_syn):
     planted = set()
     with _brain(n_syn) as b:
@@ -103,6 +105,25 @@ def test_record_count_edges(gpu, n_syn):
             whole = b.degrees()
             assert whole["out_total"] == whole["in_total"] == n_syn
     assert planted >= set(SPECIAL.view(np.uint32).tolist())
+
+
+@pytest.mark.parametrize("repeats", [True, False])
+def test_the_odd_record_after_a_whole_iteration(gpu, repeats):
+    """4097 records: the last one is alone in the second workgroup iteration, the only record of its lane, beside
+    an absent second record; every other lane of that iteration holds none.  It repeats the src and dst of record
+    4095 or shares neither, so its one add lands on a neuron that the first iteration also counted, or on one of
+    its own.  (Record 4095 is in another iteration: no shuffle of scatter() sees the two side by side.)"""
+    n_syn = 4097
+    syn = _records(n_syn, 11)
+    src, dst = int(syn["src"][4095]), int(syn["dst"][4095])
+    syn["src"][4094] = syn["src"][4096] = src if repeats else (src + 1) % 1000
+    syn["dst"][4094] = syn["dst"][4096] = dst if repeats else (dst + 1) % 1000
+    with _brain(n_syn) as b:
+        b.upload_synapses(syn)
+        for neurons in (None, (src, 2) if src < 999 else (998, 2), (dst, 1)):
+            for what in WHATS:
+                got = _against_reference(b, neurons, what, syn=syn, note=f"repeats {repeats}")
+                assert got["records"] == n_syn and got["tombstones"] == 0
 
 
 # ---- 2. both paths and the boundary ----------------------------------------------------------------

@@ -78,7 +78,9 @@ def _brain(n_syn, n_hidden=488, **kw):
 
 
 # ---- 1. record-count edges ---------------------------------------------------------------------
-@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000])
+# 4096 records are one workgroup iteration (2 x 512 threads x 4 loads): 4095 .. 4097 cross it with and without
+# the odd last record, 8193 is two iterations and that record
+@pytest.mark.parametrize("n_syn", [1, 63, 64, 65, 255, 257, 2047, 2049, 10_000, 2, 3, 4095, 4096, 4097, 8193])
 def test_record_count_edges(gpu, n_syn):
     with _brain(n_syn) as b:
         for seed in range(3 if n_syn < 3 * len(SPECIAL) else 1):

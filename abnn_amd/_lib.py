@@ -191,6 +191,22 @@ class EditConfig(C.Structure):
     ]
 
 
+REORDER_SRC, REORDER_DST, REORDER_W, REORDER_RANDOM, REORDER_NONE, REORDER_PERM = 0, 1, 2, 3, 4, 5
+REORDER_DESCENDING, REORDER_ORIGIN = 1, 2
+REORDER_HEADER_WORDS = 8
+REORDER_SCRATCH_BYTES_PER_RECORD = 28
+REORDER_KEY = 0xC2B2AE3D27D4EB4F
+
+
+class ReorderConfig(C.Structure):
+    """abnn_reorder_config -- the key, the flags and the RANDOM seed of a record reorder."""
+
+    _fields_ = [
+        ("key", C.c_uint32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 SNAP_RECORDS, SNAP_STATE = 1, 2
 DIFF_MAX_BINS = 4096
 DIFF_HEADER_WORDS = 24
@@ -378,6 +394,11 @@ SIGNATURES = [
     ("abnn_edit_host", C.c_int, [C.POINTER(EditConfig), _U64, _U64, _VP, _U64, _VP, _VP]),
     ("abnn_edit_factors_enqueue", C.c_int, [_VP, _VP, _U64, _F, _F, _F, _VP, _VP]),
     ("abnn_edit_factors_host", C.c_int, [_VP, _U64, _F, _F, _F, _VP]),
+    ("abnn_reorder_words", C.c_uint64, [C.POINTER(ReorderConfig), _U64]),
+    ("abnn_reorder_enqueue", C.c_int, [_VP, C.POINTER(ReorderConfig), _VP, _VP, _VP]),
+    ("abnn_reorder", C.c_int, [_VP, C.POINTER(ReorderConfig), _VP, _VP, _U64]),
+    ("abnn_reorder_release", C.c_int, [_VP]),
+    ("abnn_reorder_host", C.c_int, [C.POINTER(ReorderConfig), _U64, _VP, _U64, _VP, _VP]),
     ("abnn_snapshot_create", C.c_int, [_VP, C.POINTER(_VP)]),
     ("abnn_snapshot_destroy", C.c_int, [_VP]),
     ("abnn_snapshot_get_info", C.c_int, [_VP, C.POINTER(SnapshotInfo)]),
@@ -477,7 +498,9 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_snapshot_create", "abnn_snapshot_destroy", "abnn_snapshot_get_info",
                    "abnn_snapshot_capture_enqueue", "abnn_snapshot_restore", "abnn_snapshot_diff_words",
                    "abnn_snapshot_diff_enqueue", "abnn_snapshot_diff", "abnn_snapshot_diff_host",
-                   "abnn_spikes_load", "abnn_corr_words", "abnn_corr_enqueue", "abnn_corr", "abnn_corr_host")
+                   "abnn_spikes_load", "abnn_corr_words", "abnn_corr_enqueue", "abnn_corr", "abnn_corr_host",
+                   "abnn_reorder_words", "abnn_reorder_enqueue", "abnn_reorder", "abnn_reorder_release",
+                   "abnn_reorder_host")
 
 _lib = None
 

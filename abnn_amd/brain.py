@@ -20,6 +20,7 @@ from . import corr as _corr
 from . import degree as _degree
 from . import edit as _edit
 from . import hops as _hops
+from . import reorder as _reorder
 from . import select as _select
 from . import spikes as _spikes
 from ._lib import Dims, Params, Scalars, State, Stats, call
@@ -264,6 +265,43 @@ class Brain:
         edit.decode."""
         call("abnn_edit_enqueue", self._h, C.byref(cfg), int(plane_ptr) if plane_ptr else None, int(out_ptr),
              _stream_ptr(stream))
+
+    def reorder(self, key=None, descending: bool = False, seed: int = 0, origin: bool = False, perm=None) -> dict:
+        """Record reorder on the device (abnn_reorder): this
+        handle's records put into the stable order of ``key`` ('src', 'dst',
+        'w'; ``descending`` inverts it), shuffled ('random', by ``seed``),
+        compacted ('none': only the tombstones move) or permuted by ``perm``
+        (np.uint32, record k becomes the old record perm[k]; an invalid perm
+        moves nothing).  Tombstones end up last except under ``perm``; the rule
+        is in abnn.h.  Returns records, tombstones, moved, invalid, syn_offset
+        and, with ``origin``, the permutation (reorder.decode)."""
+        if perm is not None:
+            if key not in (None, "perm", _lib.REORDER_PERM):
+                raise ValueError("reorder: perm goes with no other key")
+            key = "perm"
+            perm = np.ascontiguousarray(perm, dtype=np.uint32)
+            if perm.shape != (self.n_syn(),):
+                raise ValueError("reorder: perm must hold n_syn entries")
+        elif key is None:
+            raise ValueError("reorder: a key or a perm")
+        cfg = _reorder.config(key, descending, seed, origin)
+        words = int(self._lib.abnn_reorder_words(C.byref(cfg), self.n_syn()))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_reorder", self._h, C.byref(cfg), None if perm is None else _ptr(perm), _ptr(out), words)  # an invalid config fails here
+        return _reorder.decode(out[:words], cfg)
+
+    def reorder_enqueue(self, cfg: _lib.ReorderConfig, perm_ptr: Optional[int], out_ptr: int, stream=None) -> None:
+        """Enqueue a reorder on ``stream``: the result into device memory at
+        ``out_ptr`` (abnn_reorder_words(cfg, n_syn) u64), a perm's n_syn u32
+        from device memory at ``perm_ptr`` (None otherwise); nothing
+        synchronises after the handle's first reorder.  Decode with
+        reorder.decode."""
+        call("abnn_reorder_enqueue", self._h, C.byref(cfg), int(perm_ptr) if perm_ptr else None, int(out_ptr),
+             _stream_ptr(stream))
+
+    def reorder_release(self) -> None:
+        """Free the reorder's device scratch (28 bytes per record of capacity)."""
+        call("abnn_reorder_release", self._h)
 
     def edit_factors_enqueue(self, strength_ptr: int, count: int, target: float, f_lo: float, f_hi: float,
                              plane_ptr: int, stream=None) -> None:

@@ -16,6 +16,8 @@
 * ``build_snapshot_host_test()`` : g++ -fsanitize -> tests/cpp/snapshot_host_test (the diff's host rule alone, CPU only)
 * ``build_corr_test()``   : g++ -> tests/cpp/corr_test (the correlograms' C++ mirror vs abnn_corr_host)
 * ``build_corr_host_test()`` : g++ -fsanitize -> tests/cpp/corr_host_test (the correlograms' host rule alone, CPU only)
+* ``build_reorder_test()``   : g++ -> tests/cpp/reorder_test (the record reorder's C++ mirror vs abnn_reorder_host)
+* ``build_reorder_host_test()`` : g++ -fsanitize -> tests/cpp/reorder_host_test (the reorder's host rule alone, CPU only)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -33,12 +35,12 @@ HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip")
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
                os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
-               os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip")]
+               os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip"), os.path.join(CSRC, "reorder.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
-                          os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "scan.h"),
+                          os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -75,6 +77,10 @@ CORR_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "corr_test.cpp")
 CORR_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "corr_test")
 CORR_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "corr_host_test.cpp")
 CORR_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "corr_host_test")
+REORDER_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "reorder_test.cpp")
+REORDER_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "reorder_test")
+REORDER_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "reorder_host_test.cpp")
+REORDER_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "reorder_host_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -382,6 +388,34 @@ def build_corr_host_test(force: bool = False, out: str | None = None) -> str | N
     return target
 
 
+def build_reorder_test(force: bool = False) -> str | None:
+    """Test program of the record reorder's C++ mirror (Brain::reorder,
+    ReorderView against abnn_reorder_host on the generated graph)."""
+    if not os.path.exists(REORDER_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [REORDER_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(REORDER_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", REORDER_TEST_BIN, REORDER_TEST_SRC, "-L", PKG, "-labnn_hip",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return REORDER_TEST_BIN
+
+
+def build_reorder_host_test(force: bool = False, out: str | None = None) -> str | None:
+    """The stand-alone program over the record reorder's host rule
+    (csrc/reorder.h alone: no HIP, no library), with the address and
+    undefined-behaviour sanitizers: a CPU program, run by tests/test_reorder_abi.py."""
+    if not os.path.exists(REORDER_HOST_TEST_SRC):
+        return None
+    target = out or REORDER_HOST_TEST_BIN
+    deps = [REORDER_HOST_TEST_SRC, os.path.join(CSRC, "reorder.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+    if force or out or _stale(target, deps):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-o", target, REORDER_HOST_TEST_SRC])
+    return target
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -410,6 +444,7 @@ def build_all(force: bool = False) -> None:
     build_edit_test(force)
     build_snapshot_test(force)
     build_corr_test(force)
+    build_reorder_test(force)
     build_learn_bench(force)
 
 

@@ -27,6 +27,7 @@
 #include "learn.h"
 #include "spikes.h"
 #include "corr.h"
+#include "reorder.h"
 
 using namespace abnn;
 
@@ -126,6 +127,9 @@ struct abnn_brain {
     CorrScratch corr;                // abnn_corr_*: the map, the planes, the row lists and the tallies (its first call)
     uint64_t* corr_out = nullptr;    // abnn_corr's device result, grown to the largest one asked
     uint64_t corr_cap = 0;
+    ReorderScratch reorder;          // abnn_reorder_*: the pair buffers and the records' packed copy for syn_capacity (its first call)
+    uint32_t reorder_blocks = 0;     // ... the most workgroups of its launches (4 per CU; ABNN_REORDER_BLOCKS)
+    bool reorder_skip = true;        // ... leaving out the radix passes of a constant digit (ABNN_REORDER_SKIP=0: all four)
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
     uint64_t rot = 0;              // passes run by this handle: the bitmap buffers' rotation (never reset)
@@ -183,10 +187,20 @@ abnn_status sync_all(abnn_brain* b)
     return pass_error(b);
 }
 
+void reorder_free(abnn_brain* b)
+{
+    ReorderScratch& r = b->reorder;
+    void* ptrs[] = {r.pairs[0], r.pairs[1], r.rec, r.counts, r.seg_tomb, r.state};
+    for (void* p : ptrs)
+        if (p) (void)hipFree(p);
+    r = ReorderScratch{};
+}
+
 void free_all(abnn_brain* b)
 {
     if (!b) return;
     (void)hipSetDevice(b->device);
+    reorder_free(b);
     void* ptrs[] = {b->d.syn.lo,    b->d.syn.hi,     b->d.syn.dw,     b->d.syn.src32,
                     b->d.last_fired, b->d.last_visited, b->d.visit_mark, b->scalar_block,
                     b->bitmap_buf[0], b->bitmap_buf[1], b->bitmap_buf[2], b->filter_buf[0], b->filter_buf[1],
@@ -1029,6 +1043,9 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     b->edit_blocks = 4u * (uint32_t)std::max(1, b->cus);  // as the select
     if (const char* env = std::getenv("ABNN_EDIT_BLOCKS")) b->edit_blocks = (uint32_t)std::max(1, std::atoi(env));
     if (const char* env = std::getenv("ABNN_EDIT_NT")) b->edit_nt = std::atoi(env) != 0;
+    b->reorder_blocks = 4u * (uint32_t)std::max(1, b->cus);  // as the select
+    if (const char* env = std::getenv("ABNN_REORDER_BLOCKS")) b->reorder_blocks = (uint32_t)std::max(1, std::atoi(env));
+    if (const char* env = std::getenv("ABNN_REORDER_SKIP")) b->reorder_skip = std::atoi(env) != 0;
     b->graph_blocks = 64u * (uint32_t)std::max(1, b->cus);  // measured: the finer grid evens the tail out
     if (const char* env = std::getenv("ABNN_GRAPH_BLOCKS")) b->graph_blocks = (uint32_t)std::max(1, std::atoi(env));
     if (const char* env = std::getenv("ABNN_GRAPH_NT")) b->graph_nt = std::atoi(env) != 0;
@@ -1449,6 +1466,132 @@ abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, flo
     REQUIRE((strength && plane) || count == 0, "null argument");
     REQUIRE(edit_factors_ok(target, f_lo, f_hi), "edit factors: target > 0 finite and 0 < f_lo <= f_hi finite");
     edit_factors_host(strength, count, target, f_lo, f_hi, plane);
+    return ABNN_OK;
+}
+
+/* ---- record reorder (reorder.hip) ---------------------------- */
+
+uint64_t abnn_reorder_words(const abnn_reorder_config* cfg, uint64_t n_syn) { return reorder_words(cfg, n_syn); }
+
+namespace {
+
+constexpr const char* kReorderInvalid =
+    "reorder: an unknown key or flag, DESCENDING with NONE, RANDOM or PERM, a reserved word or an unread seed that is "
+    "not 0, or more than 2^32 records";
+
+// The checks of a reorder on handle b, then its scratch (the first call
+// allocates it: that one may synchronise the device).
+abnn_status reorder_check(abnn_brain* b, const abnn_reorder_config* cfg, bool has_perm)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(reorder_words(cfg, b->dims.n_syn) != 0, kReorderInvalid);
+    REQUIRE((cfg->key == ABNN_REORDER_PERM) == has_perm, "reorder: PERM needs a perm, every other key none");
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    REQUIRE(!b->pending_walk, "reorder: a sharded pass is half done (abnn_shard_apply)");
+    HIP_TRY(hipSetDevice(b->device));
+    ReorderScratch& r = b->reorder;
+    if (r.capacity < b->dims.syn_capacity || !r.state) {
+        ST_TRY(sync_all(b));
+        reorder_free(b);
+        // no memset: a reorder writes every word it reads; whole 16-B pairs
+        const uint64_t cap = std::max<uint64_t>(b->dims.syn_capacity, 1) + 2;
+        const uint64_t sizes[] = {cap * 8, cap * 8, cap * 12,
+                                  (uint64_t)kReorderDigits * kReorderMaxSegments * 4, (kReorderMaxSegments + 1) * 4ull,
+                                  kReorderStateWords * 4ull};
+        void** slots[] = {reinterpret_cast<void**>(&r.pairs[0]), reinterpret_cast<void**>(&r.pairs[1]),
+                          reinterpret_cast<void**>(&r.rec),      reinterpret_cast<void**>(&r.counts),
+                          reinterpret_cast<void**>(&r.seg_tomb), reinterpret_cast<void**>(&r.state)};
+        for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
+            const hipError_t e = hipMalloc(slots[i], sizes[i]);
+            if (e != hipSuccess) {
+                *slots[i] = nullptr;
+                (void)hipGetLastError();
+                reorder_free(b);
+                set_err(std::string("reorder: hipMalloc(") + std::to_string(sizes[i]) + " B) of the scratch: " +
+                        hipGetErrorString(e));
+                return ABNN_ERR_OOM;
+            }
+        }
+        r.capacity = b->dims.syn_capacity;
+    }
+    return ABNN_OK;
+}
+
+// The reorder and its bookkeeping on stream s (what a records-only snapshot
+// restore redoes when n_syn is unchanged): the random-mode src mirror, the
+// pruning tally zeroed and recounted over [0, n).
+abnn_status reorder_launch(abnn_brain* b, const abnn_reorder_config* cfg, const uint32_t* perm_dev, uint64_t* out_dev,
+                           hipStream_t s)
+{
+    const uint64_t n = b->dims.n_syn;  // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_reorder(b->d.syn, n, b->dims.syn_offset, *cfg, perm_dev, b->reorder, out_dev, b->reorder_blocks,
+                           b->reorder_skip, s));
+    HIP_TRY(launch_src32_sync(b->d.syn, n, s));
+    if (b->d.dead) {
+        const uint64_t nb = (b->dims.syn_capacity + kCompactChunk - 1) / kCompactChunk;
+        HIP_TRY(hipMemsetAsync(b->d.dead, 0, nb * sizeof(uint32_t), s));
+        HIP_TRY(launch_tally_dead(b->d.syn, n, b->d.dead, 0, n, s));
+    }
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_reorder_enqueue(abnn_brain* b, const abnn_reorder_config* cfg, const uint32_t* perm_dev,
+                                 uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(reorder_check(b, cfg, perm_dev != nullptr));
+    return reorder_launch(b, cfg, perm_dev, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_reorder(abnn_brain* b, const abnn_reorder_config* cfg, const uint32_t* perm_host, uint64_t* out_host,
+                         uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(reorder_check(b, cfg, perm_host != nullptr));
+    REQUIRE(words == reorder_words(cfg, b->dims.n_syn), "abnn_reorder: words must equal abnn_reorder_words(cfg, n_syn)");
+    ST_TRY(sync_all(b));
+    // the device result and the staged perm live for this call only
+    const uint64_t n = b->dims.n_syn;
+    uint64_t* dev = nullptr;
+    uint32_t* perm_dev = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(uint64_t));
+    if (e == hipSuccess && perm_host) e = hipMalloc(reinterpret_cast<void**>(&perm_dev), std::max<uint64_t>(n, 1) * 4);
+    if (e != hipSuccess) {
+        if (dev) (void)hipFree(dev);
+        set_err(std::string("abnn_reorder: hipMalloc of the result: ") + hipGetErrorString(e));
+        return ABNN_ERR_OOM;
+    }
+    abnn_status st = ABNN_OK;
+    if (perm_host && n) e = hipMemcpyAsync(perm_dev, perm_host, n * 4, hipMemcpyHostToDevice, b->stream);
+    if (e == hipSuccess) st = reorder_launch(b, cfg, perm_dev, dev, b->stream);
+    if (e == hipSuccess && st == ABNN_OK)
+        e = hipMemcpyAsync(out_host, dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
+    const hipError_t e2 = hipStreamSynchronize(b->stream);
+    (void)hipFree(dev);
+    if (perm_dev) (void)hipFree(perm_dev);
+    ST_TRY(st);
+    HIP_TRY(e);
+    HIP_TRY(e2);
+    return ABNN_OK;
+}
+
+abnn_status abnn_reorder_release(abnn_brain* b)
+{
+    REQUIRE(b, "null argument");
+    ST_TRY(sync_all(b));
+    reorder_free(b);
+    return ABNN_OK;
+}
+
+abnn_status abnn_reorder_host(const abnn_reorder_config* cfg, uint64_t syn_offset, abnn_synapse* records, uint64_t n,
+                              const uint32_t* perm, uint64_t* out)
+{
+    REQUIRE(cfg && out && (records || n == 0), "null argument");
+    REQUIRE(reorder_words(cfg, n) != 0, kReorderInvalid);
+    REQUIRE((cfg->key == ABNN_REORDER_PERM) == (perm != nullptr), "reorder: PERM needs a perm, every other key none");
+    reorder_host(*cfg, syn_offset, records, n, perm, out);
     return ABNN_OK;
 }
 

@@ -441,6 +441,14 @@ class ShardedBrain:
         self.comm.all_reduce_sum(t)
         return dict(zip(_edit.KEYS, (int(v) for v in t.cpu().tolist())))
 
+    def reorder(self, key=None, descending: bool = False, seed: int = 0, origin: bool = False, perm=None) -> dict:
+        """Brain.reorder of this rank's own slice (every rank calls it with the
+        same arguments; ``perm`` is the rank's own, over its local indices).
+        There is no global sort across shards: a key orders each slice by
+        itself, and 'random' gives a record the key the unsharded brain gives
+        the same global index.  Returns this rank's result."""
+        return self.brain.reorder(key, descending, seed, origin, perm)
+
     def scale_inputs(self, target: float, neurons=None, limits=(0.5, 2.0)) -> dict:
         """Brain.scale_inputs over every shard's records (collective): a
         neuron's inputs lie on every rank, so the factors come from the merged

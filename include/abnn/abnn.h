@@ -611,6 +611,106 @@ abnn_status abnn_edit_host(const abnn_edit_config* cfg, uint64_t n_nrn, uint64_t
 abnn_status abnn_edit_factors_enqueue(abnn_brain* b, const uint64_t* strength_dev, uint64_t count, float target, float f_lo, float f_hi, float* plane_dev, void* stream);
 abnn_status abnn_edit_factors_host(const uint64_t* strength, uint64_t count, float target, float f_lo, float f_hi, float* plane);
 
+/* ---- record reorder: sort, shuffle, permute -------------------
+ * One operation over the handle's local records [0, n), n = n_syn, on the
+ * device.  It produces a permutation origin[0..n) of the local indices;
+ * afterwards the record at k is the old record origin[k]: src, dst and the bits
+ * of w unchanged, pad 0.  Records at and past n_syn are neither read nor
+ * written.  n_syn, the neuron state, the scalars, the statistics, the spike
+ * recorder and an engine's driver state are untouched.
+ * origin is the STABLE ascending order of the 33-bit key (tomb << 32) | k32:
+ * records with equal keys keep their old relative order.
+ *   tomb = (dst == 0xFFFFFFFF); a tombstone's k32 is 0 under every key and
+ *   direction, so the tombstones always end up last, in their old relative
+ *   order.
+ *   With ABNN_REORDER_DESCENDING a live record's k32 is replaced by ~k32 (ties
+ *   still keep their old order).
+ *   k32 of a live record by cfg.key:
+ *     ABNN_REORDER_SRC / _DST  the interchange value of src / dst
+ *     ABNN_REORDER_W       the census's order key of the bits b of w: b ^ ((b >>
+ *                          31) ? 0xFFFFFFFF : 0x80000000) -- a total order with
+ *                          -0.0 < +0.0; NaNs sort by their bits, at the two ends
+ *     ABNN_REORDER_RANDOM  (a seeded shuffle) (uint32_t)(splitmix64_at(seed ^
+ *                          ABNN_REORDER_KEY, syn_offset + k) >> 32), the graph
+ *                          builder's splitmix64_at, k the local index: a shard
+ *                          draws what the unsharded brain draws for the same
+ *                          global index
+ *     ABNN_REORDER_NONE    0: only the tombstones move, to the end (an
+ *                          order-preserving compaction)
+ *     ABNN_REORDER_PERM    no key: origin is the caller's perm (n u32).  It is
+ *                          valid only if it is a permutation of [0, n), which
+ *                          is checked on the device; an invalid one leaves the
+ *                          records exactly as they were and reports how many
+ *                          entries were out of range or repeated an earlier
+ *                          value.  Tombstones are not treated specially: PERM
+ *                          with the inverse of a returned origin undoes a
+ *                          reorder.
+ * Result, as u64 words (abnn_reorder_words = 8 + (ORIGIN ? (n_syn + 1) / 2 : 0)):
+ *   0 records (= n_syn)
+ *   1 tombstones; after the call they are exactly the records [n - T, n)
+ *     (except for PERM)
+ *   2 moved: the k with origin[k] != k
+ *   3 invalid perm entries (PERM only; non-zero: nothing moved and word 2 is 0)
+ *   4 the handle's syn_offset     5..7 zero
+ *   8 ...  with ABNN_REORDER_ORIGIN: origin as packed u32, two per word, the low
+ *          half first (the high half of the last word of an odd n is 0; after an
+ *          invalid perm it is the identity: nothing moved)
+ * Bookkeeping, in stream order after the move (what a records-only snapshot
+ * restore redoes): the random-mode src mirror is rebuilt and the pruning tally
+ * is zeroed and recounted over [0, n), so the next structural update removes the
+ * tombstones now at the end.  n_syn does not change, so the partition stays.
+ * Two consequences: a snapshot diff across a reorder pairs records by index and
+ * therefore reports them as rewired (the origin plane is how a caller maps
+ * back); and a shard reorders its own slice only -- there is no global sort
+ * across shards.
+ * Scratch: two 8-byte (key, index) buffers and a 12-byte packed copy of the
+ * records (one gather per record, not one per stream), 28 bytes per record of
+ * syn_capacity, plus about 1 MiB.                                              */
+#define ABNN_REORDER_SRC    0u
+#define ABNN_REORDER_DST    1u
+#define ABNN_REORDER_W      2u
+#define ABNN_REORDER_RANDOM 3u
+#define ABNN_REORDER_NONE   4u
+#define ABNN_REORDER_PERM   5u
+#define ABNN_REORDER_DESCENDING 1u  /* SRC, DST, W only */
+#define ABNN_REORDER_ORIGIN     2u  /* also return origin */
+#define ABNN_REORDER_HEADER_WORDS 8
+#define ABNN_REORDER_SCRATCH_BYTES_PER_RECORD 28
+#define ABNN_REORDER_KEY 0xC2B2AE3D27D4EB4Full
+typedef struct abnn_reorder_config {     /* 32 bytes */
+    uint32_t key, flags;
+    uint64_t seed;                       /* RANDOM only; else 0 */
+    uint32_t reserved[4];                /* 0 */
+} abnn_reorder_config;
+/* 8 + (ORIGIN ? (n_syn + 1) / 2 : 0), or 0 for what can be refused without a
+ * handle: null, an unknown key or flag bit, DESCENDING with NONE, RANDOM or
+ * PERM, a reserved word or an unread seed that is not 0, n_syn > 2^32 (local
+ * indices are u32).                                                            */
+uint64_t    abnn_reorder_words(const abnn_reorder_config* cfg, uint64_t n_syn);
+/* Enqueue only: everything runs in stream order on `stream`; no workgroup waits
+ * for another and nothing synchronises, so it can sit between passes and
+ * between abnn_engine_run calls.  perm_dev: PERM's n u32 in DEVICE memory, NULL
+ * otherwise.  out_dev: DEVICE memory of abnn_reorder_words(cfg, n_syn) u64.
+ * The handle owns the scratch, sized for syn_capacity: the FIRST reorder call
+ * on a handle allocates it and may synchronise the device; abnn_brain_destroy
+ * and abnn_reorder_release free it.  Two reorders of one handle enqueued on
+ * different streams must be ordered by the caller.
+ * ABNN_ERR_INVALID: a null argument, what abnn_reorder_words refuses, perm_dev
+ * null with PERM or non-null without it, a handle whose records are invalid, a
+ * sharded pass half done.  ABNN_ERR_OOM for the scratch leaves the records
+ * untouched.  n_syn == 0 is valid.                                             */
+abnn_status abnn_reorder_enqueue(abnn_brain* b, const abnn_reorder_config* cfg, const uint32_t* perm_dev, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: perm_host is PERM's n u32 on the host (else NULL),
+ * out_host holds `words` u64 (== abnn_reorder_words(cfg, n_syn)).              */
+abnn_status abnn_reorder(abnn_brain* b, const abnn_reorder_config* cfg, const uint32_t* perm_host, uint64_t* out_host, uint64_t words);
+/* Frees the reorder's scratch early (synchronises the device first); the next
+ * reorder allocates it again.                                                  */
+abnn_status abnn_reorder_release(abnn_brain* b);
+/* The rule on the host, without a device or a handle, over n interchange
+ * records in place (local record k has global index syn_offset + k; perm: PERM's
+ * n u32, else NULL); out holds abnn_reorder_words(cfg, n) u64.  A std::stable_sort. */
+abnn_status abnn_reorder_host(const abnn_reorder_config* cfg, uint64_t syn_offset, abnn_synapse* records, uint64_t n, const uint32_t* perm, uint64_t* out);
+
 /* ---- device-side snapshots: capture, roll back, diff ----------
  * A snapshot keeps a copy of a handle's state in device memory: the records
  * [0, n_syn) (11 B each: the two src streams and {dst, w}), the two timestamp

@@ -134,6 +134,20 @@ struct EditView {
     uint64_t nonfinite() const { return words[5]; }  // non-zero: the edit stored a NaN or an inf
 };
 
+// A view of a reorder result (abnn.h abnn_reorder: the header and, with
+// ABNN_REORDER_ORIGIN, the permutation as packed u32); it does not own the words.
+struct ReorderView {
+    const uint64_t* words = nullptr;
+    explicit ReorderView(const uint64_t* w) : words(w) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }  // afterwards the last ones, except under PERM
+    uint64_t moved() const { return words[2]; }
+    uint64_t invalid() const { return words[3]; }  // PERM: entries out of range or repeated; non-zero: nothing moved
+    uint64_t syn_offset() const { return words[4]; }
+    // with ABNN_REORDER_ORIGIN: the record at k is the old record origin()[k]
+    const uint32_t* origin() const { return reinterpret_cast<const uint32_t*>(words + ABNN_REORDER_HEADER_WORDS); }
+};
+
 // A view of a reachability result (abnn.h abnn_hops: the header, the levels
 // and the distance plane); it does not own the words.
 struct HopsView {
@@ -596,6 +610,26 @@ public:
     void edit_enqueue(const abnn_edit_config& cfg, const float* plane_dev, uint64_t* out_dev, void* stream = nullptr)
     {
         check(abnn_edit_enqueue(h_, &cfg, plane_dev, out_dev, stream), "abnn_edit_enqueue");
+    }
+    // Record reorder on the device (abnn_reorder; the rule is in abnn.h): the
+    // records in the stable order of cfg's key, shuffled, compacted or (perm:
+    // n_syn u32) permuted; the result's words, to be read through a ReorderView.
+    std::vector<uint64_t> reorder(const abnn_reorder_config& cfg, const std::vector<uint32_t>& perm = {})
+    {
+        abnn_dims d{};
+        check(abnn_get_dims(h_, &d), "abnn_get_dims");
+        const uint64_t words = abnn_reorder_words(&cfg, d.n_syn);
+        std::vector<uint64_t> w(words ? words : 1);
+        const bool has_perm = cfg.key == ABNN_REORDER_PERM;
+        check(abnn_reorder(h_, &cfg, has_perm ? perm.data() : nullptr, w.data(), words), "abnn_reorder");
+        return w;
+    }
+    // Enqueue only: perm_dev (PERM's n_syn u32, else null) and out_dev
+    // (abnn_reorder_words(&cfg, n_syn) u64) are device memory.
+    void reorder_enqueue(const abnn_reorder_config& cfg, const uint32_t* perm_dev, uint64_t* out_dev,
+                         void* stream = nullptr)
+    {
+        check(abnn_reorder_enqueue(h_, &cfg, perm_dev, out_dev, stream), "abnn_reorder_enqueue");
     }
     // Enqueue only: `count` strength words of a degree census (device memory) into factors target / strength
     // clamped to [f_lo, f_hi] at plane_dev.

@@ -531,6 +531,7 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_raw_fused", C.c_int, [C.c_int]),
     ("abnn_debug_raw_fused_active", C.c_int, []),
     ("abnn_debug_raw_wave_clock", C.c_int, [_VP, C.c_uint64, _U32, _U32, C.POINTER(C.c_uint64), C.c_uint64, _VP]),
+    ("abnn_debug_live_allocations", C.c_uint64, []),
 ]
 
 

@@ -40,7 +40,7 @@ HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "de
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
-                          os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"),
+                          os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "pool.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")

@@ -28,14 +28,15 @@
 #include "spikes.h"
 #include "corr.h"
 #include "reorder.h"
+#include "pool.h"
 
 using namespace abnn;
 
+static thread_local std::string g_err;
+
+void abnn::set_err(const std::string& m) { g_err = m; }
+
 namespace {
-
-thread_local std::string g_err;
-
-void set_err(const std::string& m) { g_err = m; }
 
 #define HIP_TRY(expr)                                                                  \
     do {                                                                               \
@@ -74,6 +75,7 @@ struct abnn_brain {
     int device = 0;
     hipStream_t stream = nullptr;  // default stream of state accessors (the null stream)
     uint64_t n_nrn = 0;
+    DevicePool pool;               // owns every device buffer below and in d, select, spikes, corr, reorder (pool.h)
     DeviceState d{};
     void* scalar_block = nullptr;  // clock | reward | rbar
     uint64_t clock_host = 0;       // mirror, for the renormalisation decision (brain.cpp:127)
@@ -159,6 +161,18 @@ struct abnn_brain {
     // reloaded (abnn_load_bnn / abnn_load_flat / abnn_generate_synapses / an
     // upload of every record)
     bool records_invalid = false;
+
+    // On the handle's device.  The device memory goes with the pool; the rest
+    // is the timing events and the error word.
+    ~abnn_brain()
+    {
+        pool.release_all();
+        for (auto& e : events) {
+            (void)hipEventDestroy(e.a);
+            (void)hipEventDestroy(e.b);
+        }
+        if (err_host) (void)hipHostFree(err_host);
+    }
 };
 
 namespace {
@@ -190,56 +204,8 @@ abnn_status sync_all(abnn_brain* b)
 void reorder_free(abnn_brain* b)
 {
     ReorderScratch& r = b->reorder;
-    void* ptrs[] = {r.pairs[0], r.pairs[1], r.rec, r.counts, r.seg_tomb, r.state};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    b->pool.release(&r.pairs[0], &r.pairs[1], &r.rec, &r.counts, &r.seg_tomb, &r.state);
     r = ReorderScratch{};
-}
-
-void free_all(abnn_brain* b)
-{
-    if (!b) return;
-    (void)hipSetDevice(b->device);
-    reorder_free(b);
-    void* ptrs[] = {b->d.syn.lo,    b->d.syn.hi,     b->d.syn.dw,     b->d.syn.src32,
-                    b->d.last_fired, b->d.last_visited, b->d.visit_mark, b->scalar_block,
-                    b->bitmap_buf[0], b->bitmap_buf[1], b->bitmap_buf[2], b->filter_buf[0], b->filter_buf[1],
-                    b->filter_buf[2], b->cost_buf[0], b->cost_buf[1], b->d.lb_status, b->d.cand_list,
-                    b->d.range_info,    b->d.range_g1,  b->d.g2x,
-                    b->d.chunk_cnt,
-                    b->d.wg_stats, b->d.claim,  b->d.g2src,      b->d.grown,
-                    b->d.dead,      b->compact_offsets, b->swap_part, b->swap_toff, b->span_words, b->grown_cnt,
-                    b->d.work,      b->idx_scratch,
-                    b->u64_scratch,  b->census_out, b->degree_out, b->select.counts, b->select.offsets, b->edit_plane, b->edit_out, b->diff_out, b->hops_bitmap, b->hops_out, b->spikes.words, b->spikes.passes, b->spikes.raster, b->spikes.counts,
-                    b->corr.map, b->corr.cnt, b->corr.off, b->corr.cur, b->corr.rows, b->corr.tally, b->corr.cursor, b->corr_out,
-                    b->d.wave_clock,  b->d.apply_clock, b->d.fired_ring, b->d.n_fired_ring, b->d.range_bounds,  b->d.range_bounds_next, b->d.range_bounds_prev,
-                    const_cast<uint32_t*>(b->d.dummy)};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (auto& e : b->events) {
-        (void)hipEventDestroy(e.a);
-        (void)hipEventDestroy(e.b);
-    }
-    if (b->err_host) (void)hipHostFree(b->err_host);
-}
-
-template <typename T>
-abnn_status dalloc(T** p, uint64_t count)
-{
-    if (count == 0) count = 1;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(p), count * sizeof(T));
-    if (e != hipSuccess) {
-        *p = nullptr;
-        set_err(std::string("hipMalloc(") + std::to_string(count * sizeof(T)) + " B): " +
-                hipGetErrorString(e));
-        return ABNN_ERR_OOM;
-    }
-    e = hipMemset(*p, 0, count * sizeof(T));
-    if (e != hipSuccess) {
-        set_err(std::string("hipMemset: ") + hipGetErrorString(e));
-        return ABNN_ERR_HIP;
-    }
-    return ABNN_OK;
 }
 
 #define ST_TRY(expr)                        \
@@ -248,40 +214,29 @@ abnn_status dalloc(T** p, uint64_t count)
         if (_s != ABNN_OK) return _s;       \
     } while (0)
 
-// A device buffer that grows to the largest count asked: *p holds *cap entries.
-template <typename T>
-abnn_status grow(T** p, uint64_t* cap, uint64_t count)
+// The tail of a synchronous call: `words` u64 of its device result to the host
+// on the handle's stream, then the wait for them.
+abnn_status read_words(abnn_brain* b, const uint64_t* dev, uint64_t* out_host, uint64_t words)
 {
-    if (count <= *cap) return ABNN_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    ST_TRY(dalloc(p, count));
-    *cap = count;
+    HIP_TRY(hipMemcpyAsync(out_host, dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+    HIP_TRY(hipStreamSynchronize(b->stream));
     return ABNN_OK;
 }
 
-abnn_status ensure_idx_scratch(abnn_brain* b, uint64_t n) { return grow(&b->idx_scratch, &b->idx_cap, n); }
+abnn_status ensure_idx_scratch(abnn_brain* b, uint64_t n) { return b->pool.grow(&b->idx_scratch, &b->idx_cap, n); }
 
 // a src / dst range of a config: not set (count 0), or inside [0, n_nrn)
 inline bool range_ok(uint32_t first, uint32_t count, uint64_t n_nrn) { return !count || (uint64_t)first + count <= n_nrn; }
 
 // Device records are the packed src streams, dst and w (SynArrays, engine.h);
 // abnn_synapse is the host interchange format.  Capacity `count` records.
-abnn_status alloc_syn(SynArrays* a, uint64_t count, bool random_mode)
+abnn_status alloc_syn(DevicePool& pool, SynArrays* a, uint64_t count, bool random_mode)
 {
-    ST_TRY(dalloc(&a->lo, count));
-    ST_TRY(dalloc(&a->hi, hi_bytes(count)));
-    if (random_mode) ST_TRY(dalloc(&a->src32, count));
-    return dalloc(&a->dw, count);
+    ST_TRY(pool.alloc(zeroed(&a->lo, count)));
+    ST_TRY(pool.alloc(zeroed(&a->hi, hi_bytes(count))));
+    if (random_mode) ST_TRY(pool.alloc(zeroed(&a->src32, count)));
+    return pool.alloc(zeroed(&a->dw, count));
 }
-
-// src values of records [first, first + m) <-> host u32 (interchange form),
-// through a device staging buffer and the pack / unpack kernels.
-struct SrcStage {
-    uint32_t* dev = nullptr;
-    ~SrcStage() { if (dev) (void)hipFree(dev); }
-};
 
 // Chunked copies between device arrays [first, first + n) and host records.
 constexpr uint64_t kXferRecs = 1u << 22;
@@ -290,8 +245,8 @@ abnn_status records_d2h(const SynArrays& a, uint64_t first, uint64_t n, abnn_syn
 {
     std::vector<uint32_t> s;
     std::vector<uint2> dw;
-    SrcStage st;
-    if (n) ST_TRY(dalloc(&st.dev, std::min<uint64_t>(kXferRecs, n)));
+    DeviceTemp<uint32_t> st;  // the chunk's src values as u32, for the pack / unpack kernels
+    if (n) ST_TRY(st.alloc(std::min<uint64_t>(kXferRecs, n)));
     for (uint64_t i = 0; i < n; i += kXferRecs) {
         const uint64_t m = std::min<uint64_t>(kXferRecs, n - i);
         s.resize(m);
@@ -312,8 +267,8 @@ abnn_status records_h2d(const SynArrays& a, uint64_t first, uint64_t n, const ab
 {
     std::vector<uint32_t> s;
     std::vector<uint2> dw;
-    SrcStage st;
-    if (n) ST_TRY(dalloc(&st.dev, std::min<uint64_t>(kXferRecs, n)));
+    DeviceTemp<uint32_t> st;  // the chunk's src values as u32, for the pack / unpack kernels
+    if (n) ST_TRY(st.alloc(std::min<uint64_t>(kXferRecs, n)));
     for (uint64_t i = 0; i < n; i += kXferRecs) {
         const uint64_t m = std::min<uint64_t>(kXferRecs, n - i);
         s.resize(m);
@@ -376,7 +331,7 @@ constexpr const char* kRecordsInvalid =
 abnn_status ensure_visit_marks(abnn_brain* b)
 {
     if (!b->params.track_visits || b->d.visit_mark) return ABNN_OK;
-    return dalloc(&b->d.visit_mark, b->n_nrn);
+    return b->pool.alloc(zeroed(&b->d.visit_mark, b->n_nrn));
 }
 
 void host_tick(abnn_brain* b)
@@ -449,6 +404,68 @@ abnn_status reset_ranges(abnn_brain* b)
     for (uint32_t r = 0; r <= d.n_ranges; ++r) rb[r] = (uint32_t)((uint64_t)r * d.iters / std::max(1u, d.n_ranges));
     HIP_TRY(hipMemcpy(d.range_bounds, rb.data(), rb.size() * 4, hipMemcpyHostToDevice));
     return ABNN_OK;
+}
+
+// build_buffers, brain.cpp:52-69: allocate and zero every buffer of a new
+// handle (its pool frees what a failure leaves), then the uniform partition.
+// `slots`: the most events a pass visits, in whole wave iterations.
+abnn_status brain_buffers(abnn_brain* b, uint64_t slots, uint64_t max_ranges, bool genesis)
+{
+    DeviceState& d = b->d;
+    DevicePool& pool = b->pool;
+    const abnn_params& p = b->params;
+    const uint64_t n_nrn = b->n_nrn, cap = b->dims.syn_capacity;
+    // padded: the gate's last iteration reads up to one iteration past the sweep
+    ST_TRY(alloc_syn(pool, &d.syn, cap + kDummyRecords, p.mode == ABNN_MODE_RANDOM));
+    ST_TRY(pool.alloc_all({zeroed(&d.last_fired, n_nrn), zeroed(&d.last_visited, n_nrn)}));
+    // a shard (global_events set) that tracks visits marks them for the merge
+    if (p.track_visits && b->dims.global_events) ST_TRY(pool.alloc(zeroed(&d.visit_mark, n_nrn)));
+    uint64_t* sb = nullptr;
+    ST_TRY(pool.alloc(zeroed(&sb, 3)));  // {clock, reward|rbar, pass_index}
+    b->scalar_block = sb;
+    d.clock = sb;
+    d.reward = reinterpret_cast<float*>(sb + 1);
+    d.rbar = d.reward + 1;
+    d.pass_index = sb + 2;
+    for (int i = 0; i < 3; ++i)
+        ST_TRY(pool.alloc_all({zeroed(&b->bitmap_buf[i], d.n_bitmap_words + 2ull), zeroed(&b->filter_buf[i], 2 * kMaxFilterWords)}));
+    d.bitmap = b->bitmap_buf[0];
+    d.filter = b->filter_buf[0];
+    uint32_t* dummy = nullptr;
+    // g2x: per-range regions of refractory survivors (16 B per event: every
+    // event of a range may pass in the warm-up passes)
+    ST_TRY(pool.alloc_all({zeroed(&b->cost_buf[0], max_ranges), zeroed(&b->cost_buf[1], max_ranges),
+                           zeroed(&d.lb_status, kMaxGateBlocks), zeroed(&d.cand_list, (uint64_t)kFusedMaxRanges * kCandCap),
+                           zeroed(&d.range_info, max_ranges), zeroed(&d.range_g1, max_ranges), zeroed(&d.g2x, slots),
+                           zeroed(&d.chunk_cnt, slots / kChunkSlotDiv + 8), zeroed(&dummy, 2 * kDummyRecords),
+                           zeroed(&d.wg_stats, kWalkBlocks)}));
+    d.dummy = dummy;
+    if (p.mode == ABNN_MODE_RANDOM) ST_TRY(pool.alloc(zeroed(&d.claim, cap)));
+    if (p.compact_every > 0) {
+        // structural updates (in place): the span's offsets (<= nb used, + slack), the scan's sums, the tail blocks'
+        // prefix (+ 1 <= nb + 2), the device words; the tombstone tally: pruning's, and an upload's (a saved pruned brain)
+        const uint64_t nb = (cap + kCompactChunk - 1) / kCompactChunk;
+        ST_TRY(pool.alloc_all({zeroed(&b->compact_offsets, nb + 4), zeroed(&b->swap_part, (nb + kScanThreads - 1) / kScanThreads + 1),
+                               zeroed(&b->swap_toff, nb + 4), zeroed(&b->span_words, 8), zeroed(&d.dead, nb)}));
+    }
+    if (genesis) {
+        const uint64_t grown = (uint64_t)p.compact_every * p.max_spikes;
+        ST_TRY(pool.alloc_all({zeroed(&d.g2src, slots), zeroed(&d.grown, grown),
+                               zeroed(&b->grown_cnt, (grown + kScanThreads - 1) / kScanThreads + 1)}));
+    }
+    ST_TRY(pool.alloc(zeroed(&d.work, 1)));
+    if (hipHostMalloc(reinterpret_cast<void**>(&b->err_host), 4, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+        hipHostGetDevicePointer(reinterpret_cast<void**>(&d.err_word), b->err_host, 0) != hipSuccess) {
+        set_err("hipHostMalloc (error word) failed");
+        return ABNN_ERR_OOM;
+    }
+    *b->err_host = 0;
+    ST_TRY(pool.alloc_all({zeroed(&b->u64_scratch, 4), zeroed(&d.wave_clock, (uint64_t)kWaveClockPasses * kWaveClock * kMaxRanges + 32),
+                           zeroed(&d.apply_clock, 8 * (uint64_t)kWalkBlocks),
+                           zeroed(&d.fired_ring, (uint64_t)kFiredRing * std::max(1u, p.max_spikes)),
+                           zeroed(&d.n_fired_ring, kFiredRing), zeroed(&d.range_bounds, max_ranges + 1),
+                           zeroed(&d.range_bounds_next, max_ranges + 1), zeroed(&d.range_bounds_prev, max_ranges + 1)}));
+    return reset_ranges(b);
 }
 
 // The sweep partition after dims.n_syn changed (a structural update, a
@@ -901,6 +918,7 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     }
     REQUIRE(device >= 0 && device < ndev, "device ordinal out of range");
 
+    HIP_TRY(hipSetDevice(device));
     abnn_brain* b = new (std::nothrow) abnn_brain();
     if (!b) return ABNN_ERR_OOM;
     b->dims = *dims;
@@ -910,15 +928,6 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     b->device = device;
     b->n_nrn = n_nrn;
     b->rng = p.seed;
-    auto fail = [&](abnn_status s) {
-        free_all(b);
-        delete b;
-        return s;
-    };
-    if (hipSetDevice(device) != hipSuccess) {
-        set_err("hipSetDevice failed");
-        return fail(ABNN_ERR_HIP);
-    }
     DeviceState& d = b->d;
     d.n_nrn = n_nrn;
     d.n_input = dims->n_input;
@@ -959,29 +968,6 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     d.n_bitmap_words = (uint32_t)(2 * ((n_nrn + 63) / 64));
     d.filter_words = filter_words;
     d.filter_log2 = (uint32_t)__builtin_ctz(filter_words);
-    abnn_status s;
-    // build_buffers, brain.cpp:52-69: allocate and zero every buffer.
-    // padded: the gate's last iteration reads up to one iteration past the sweep
-    if ((s = alloc_syn(&d.syn, cap + kDummyRecords, p.mode == ABNN_MODE_RANDOM)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.last_fired, n_nrn)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.last_visited, n_nrn)) != ABNN_OK) return fail(s);
-    // a shard (global_events set) that tracks visits marks them for the merge
-    if (p.track_visits && dims->global_events && (s = dalloc(&d.visit_mark, n_nrn)) != ABNN_OK) return fail(s);
-    uint64_t* sb = nullptr;
-    if ((s = dalloc(&sb, 3)) != ABNN_OK) return fail(s);  // {clock, reward|rbar, pass_index}
-    b->scalar_block = sb;
-    d.clock = sb;
-    d.reward = reinterpret_cast<float*>(sb + 1);
-    d.rbar = d.reward + 1;
-    d.pass_index = sb + 2;
-    for (int i = 0; i < 3; ++i) {
-        if ((s = dalloc(&b->bitmap_buf[i], (uint64_t)d.n_bitmap_words + 2)) != ABNN_OK) return fail(s);
-        if ((s = dalloc(&b->filter_buf[i], 2 * kMaxFilterWords)) != ABNN_OK) return fail(s);
-    }
-    for (int i = 0; i < 2; ++i)
-        if ((s = dalloc(&b->cost_buf[i], max_ranges)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.lb_status, kMaxGateBlocks)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.cand_list, (uint64_t)kFusedMaxRanges * kCandCap)) != ABNN_OK) return fail(s);
     if (const char* env = std::getenv("ABNN_FUSED")) b->use_fused = std::atoi(env) != 0;
     d.spec_mode = 1;
     d.spec_margin = -1;
@@ -992,51 +978,7 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     d.lean = 1;
     if (const char* env = std::getenv("ABNN_LEAN")) d.lean = std::atoi(env) != 0;
     if (const char* env = std::getenv("ABNN_SPEC")) d.spec_mode = (uint32_t)std::min(2, std::max(0, std::atoi(env)));
-    d.bitmap = b->bitmap_buf[0];
-    d.filter = b->filter_buf[0];
-    if ((s = dalloc(&d.range_info, max_ranges)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.range_g1, max_ranges)) != ABNN_OK) return fail(s);
-    // per-range regions of refractory survivors (16 B per event: every event of
-    // a range may pass in the warm-up passes)
-    if ((s = dalloc(&d.g2x, iters * iter_events)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.chunk_cnt, iters * iter_events / kChunkSlotDiv + 8)) != ABNN_OK) return fail(s);
-    uint32_t* dummy = nullptr;
-    if ((s = dalloc(&dummy, 2 * kDummyRecords)) != ABNN_OK) return fail(s);
-    d.dummy = dummy;
-    if ((s = dalloc(&d.wg_stats, kWalkBlocks)) != ABNN_OK) return fail(s);
-    if (p.mode == ABNN_MODE_RANDOM && (s = dalloc(&d.claim, cap)) != ABNN_OK) return fail(s);
-    if (p.compact_every > 0) {  // structural updates (in place): the span's offsets, read flags, words
-        const uint64_t nb = (cap + kCompactChunk - 1) / kCompactChunk;
-        if ((s = dalloc(&b->compact_offsets, nb + 4)) != ABNN_OK) return fail(s);  // <= nb used (+ slack)
-        if ((s = dalloc(&b->swap_part, (nb + kScanThreads - 1) / kScanThreads + 1)) != ABNN_OK) return fail(s);
-        if ((s = dalloc(&b->swap_toff, nb + 4)) != ABNN_OK) return fail(s);  // tail blocks + 1 <= nb + 2
-        if ((s = dalloc(&b->span_words, 8)) != ABNN_OK) return fail(s);
-        // the tombstone tally: pruning's, and an upload's (a saved pruned brain)
-        if ((s = dalloc(&d.dead, nb)) != ABNN_OK) return fail(s);
-    }
-    if (genesis) {
-        if ((s = dalloc(&d.g2src, iters * iter_events)) != ABNN_OK) return fail(s);
-        if ((s = dalloc(&d.grown, (uint64_t)p.compact_every * p.max_spikes)) != ABNN_OK) return fail(s);
-        if ((s = dalloc(&b->grown_cnt, ((uint64_t)p.compact_every * p.max_spikes + kScanThreads - 1) / kScanThreads + 1)) !=
-            ABNN_OK)
-            return fail(s);
-    }
-    if ((s = dalloc(&d.work, 1)) != ABNN_OK) return fail(s);
-    if (hipHostMalloc(reinterpret_cast<void**>(&b->err_host), 4, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-        hipHostGetDevicePointer(reinterpret_cast<void**>(&d.err_word), b->err_host, 0) != hipSuccess) {
-        set_err("hipHostMalloc (error word) failed");
-        return fail(ABNN_ERR_OOM);
-    }
-    *b->err_host = 0;
-    if ((s = dalloc(&b->u64_scratch, 4)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.wave_clock, (uint64_t)kWaveClockPasses * kWaveClock * kMaxRanges + 32)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.apply_clock, 8 * (uint64_t)kWalkBlocks)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.fired_ring, (uint64_t)kFiredRing * std::max(1u, p.max_spikes))) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.n_fired_ring, kFiredRing)) != ABNN_OK) return fail(s);
     b->force_full_bitmap = std::getenv("ABNN_FULL_BITMAP") != nullptr;
-    if ((s = dalloc(&d.range_bounds, max_ranges + 1)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.range_bounds_next, max_ranges + 1)) != ABNN_OK) return fail(s);
-    if ((s = dalloc(&d.range_bounds_prev, max_ranges + 1)) != ABNN_OK) return fail(s);
     d.adapt_ranges = std::getenv("ABNN_STATIC_RANGES") ? 0u : 1u;
     b->select_blocks = 4u * (uint32_t)std::max(1, b->cus);  // 32 waves per CU, as the census
     if (const char* env = std::getenv("ABNN_SELECT_BLOCKS")) b->select_blocks = (uint32_t)std::max(1, std::atoi(env));
@@ -1049,7 +991,11 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     b->graph_blocks = 64u * (uint32_t)std::max(1, b->cus);  // measured: the finer grid evens the tail out
     if (const char* env = std::getenv("ABNN_GRAPH_BLOCKS")) b->graph_blocks = (uint32_t)std::max(1, std::atoi(env));
     if (const char* env = std::getenv("ABNN_GRAPH_NT")) b->graph_nt = std::atoi(env) != 0;
-    if ((s = reset_ranges(b)) != ABNN_OK) return fail(s);
+    const abnn_status s = brain_buffers(b, iters * iter_events, max_ranges, genesis);
+    if (s != ABNN_OK) {
+        delete b;
+        return s;
+    }
     *out = b;
     return ABNN_OK;
 }
@@ -1059,7 +1005,6 @@ abnn_status abnn_brain_destroy(abnn_brain* b)
     if (!b) return ABNN_OK;
     (void)hipSetDevice(b->device);
     (void)hipDeviceSynchronize();
-    free_all(b);
     delete b;
     return ABNN_OK;
 }
@@ -1261,11 +1206,9 @@ abnn_status abnn_census(abnn_brain* b, const abnn_census_config* cfg, uint64_t* 
     ST_TRY(census_check(b, cfg, &scale));
     REQUIRE(words == abnn_census_words(cfg), "abnn_census: words must equal abnn_census_words(cfg)");
     ST_TRY(sync_all(b));
-    if (!b->census_out) ST_TRY(dalloc(&b->census_out, ABNN_CENSUS_HEADER_WORDS + ABNN_CENSUS_MAX_BINS));
+    if (!b->census_out) ST_TRY(b->pool.alloc(zeroed(&b->census_out, ABNN_CENSUS_HEADER_WORDS + ABNN_CENSUS_MAX_BINS)));
     HIP_TRY(launch_census(b->d.syn, b->dims.n_syn, *cfg, scale, b->census_out, (uint32_t)b->cus, b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->census_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->census_out, out_host, words);
 }
 
 /* ---- neuron degree census (degree.hip) ---------------------- */
@@ -1301,11 +1244,9 @@ abnn_status abnn_degree(abnn_brain* b, const abnn_degree_config* cfg, uint64_t* 
     ST_TRY(degree_check(b, cfg));
     REQUIRE(words == degree_words(cfg, b->n_nrn), "abnn_degree: words must equal abnn_degree_words(cfg, N_NRN)");
     ST_TRY(sync_all(b));
-    ST_TRY(grow(&b->degree_out, &b->degree_cap, words));
+    ST_TRY(b->pool.grow(&b->degree_out, &b->degree_cap, words));
     HIP_TRY(launch_degree(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->degree_out, (uint32_t)b->cus, b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->degree_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->degree_out, out_host, words);
 }
 
 /* ---- synapse select (select.hip) ---------------------------- */
@@ -1326,14 +1267,11 @@ abnn_status select_check(abnn_brain* b, const abnn_select_config* cfg, uint64_t 
     REQUIRE(range_ok(cfg->dst_first, cfg->dst_count, b->n_nrn), "select: dst range ends above N_NRN");
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     HIP_TRY(hipSetDevice(b->device));
+    if (b->select.counts) return ABNN_OK;
     // no memset: a select zeroes the counts it reads and writes the offsets it reads
-    if (!b->select.counts)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->select.counts),
-                          std::max<uint64_t>(4, select_count_words(b->dims.syn_capacity)) * sizeof(uint32_t)));
-    if (!b->select.offsets)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->select.offsets),
-                          std::max<uint64_t>(1, select_tiles(b->dims.syn_capacity)) * sizeof(uint64_t)));
-    return ABNN_OK;
+    return b->pool.alloc_all(
+        {raw(&b->select.counts, std::max<uint64_t>(4, select_count_words(b->dims.syn_capacity))),
+         raw(&b->select.offsets, select_tiles(b->dims.syn_capacity))});
 }
 
 }  // namespace
@@ -1357,28 +1295,20 @@ abnn_status abnn_select(abnn_brain* b, const abnn_select_config* cfg, uint64_t c
     REQUIRE(words == select_words(cfg, capacity), "abnn_select: words must equal abnn_select_words(cfg, capacity)");
     ST_TRY(sync_all(b));
     // the device result lives for this call only: a capacity of every record is 24 B per record
-    uint64_t* dev = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(uint64_t));
-    if (e != hipSuccess) {
-        set_err(std::string("abnn_select: hipMalloc(") + std::to_string(words * sizeof(uint64_t)) + " B): " +
-                hipGetErrorString(e));
-        return ABNN_ERR_OOM;
-    }
-    e = launch_select(b->d.syn, b->dims.n_syn, b->dims.syn_offset, *cfg, capacity, b->select, dev, b->select_blocks,
-                      b->stream);
+    DeviceTemp<uint64_t> res;
+    ST_TRY(res.alloc(words, false));  // no memset: launch_select zeroes the header, the rest is read up to `written`
+    uint64_t* dev = res.dev;
+    HIP_TRY(launch_select(b->d.syn, b->dims.n_syn, b->dims.syn_offset, *cfg, capacity, b->select, dev, b->select_blocks,
+                          b->stream));
     const uint64_t h = ABNN_SELECT_HEADER_WORDS;
-    if (e == hipSuccess) e = hipMemcpyAsync(out_host, dev, h * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
-    const uint64_t written = e == hipSuccess ? out_host[3] : 0;
-    if (e == hipSuccess && written) {  // the header, then only the entries that were written
-        e = hipMemcpyAsync(out_host + h, dev + h, written * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(out_host + h + capacity, dev + h + capacity, written * sizeof(abnn_synapse),
-                               hipMemcpyDeviceToHost, b->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(b->stream);
+    ST_TRY(read_words(b, dev, out_host, h));
+    const uint64_t written = out_host[3];
+    if (written) {  // the header, then only the entries that were written
+        HIP_TRY(hipMemcpyAsync(out_host + h, dev + h, written * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipMemcpyAsync(out_host + h + capacity, dev + h + capacity, written * sizeof(abnn_synapse),
+                               hipMemcpyDeviceToHost, b->stream));
+        HIP_TRY(hipStreamSynchronize(b->stream));
     }
-    (void)hipFree(dev);
-    HIP_TRY(e);
     return ABNN_OK;
 }
 
@@ -1428,17 +1358,14 @@ abnn_status abnn_edit(abnn_brain* b, const abnn_edit_config* cfg, const float* p
             "abnn_edit: plane_count must equal the neurons of the SCALE op's range (N_NRN when it is not set), 0 otherwise");
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     ST_TRY(sync_all(b));
-    if (!b->edit_out) ST_TRY(dalloc(&b->edit_out, ABNN_EDIT_HEADER_WORDS));
-    ST_TRY(grow(&b->edit_plane, &b->edit_plane_cap, plane_count));
+    if (!b->edit_out) ST_TRY(b->pool.alloc(zeroed(&b->edit_out, ABNN_EDIT_HEADER_WORDS)));
+    ST_TRY(b->pool.grow(&b->edit_plane, &b->edit_plane_cap, plane_count));
     if (plane_count)
         HIP_TRY(hipMemcpyAsync(b->edit_plane, plane_host, plane_count * sizeof(float), hipMemcpyHostToDevice, b->stream));
     HIP_TRY(launch_edit(b->d.syn, b->dims.n_syn, edit_rule(*cfg, b->n_nrn, b->dims.syn_offset),
                         plane_count ? b->edit_plane : nullptr, b->d.dead, b->edit_out, b->edit_blocks, b->edit_nt,
                         b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->edit_out, ABNN_EDIT_HEADER_WORDS * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                           b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->edit_out, out_host, ABNN_EDIT_HEADER_WORDS);
 }
 
 abnn_status abnn_edit_host(const abnn_edit_config* cfg, uint64_t n_nrn, uint64_t syn_offset, abnn_synapse* records,
@@ -1495,23 +1422,9 @@ abnn_status reorder_check(abnn_brain* b, const abnn_reorder_config* cfg, bool ha
         reorder_free(b);
         // no memset: a reorder writes every word it reads; whole 16-B pairs
         const uint64_t cap = std::max<uint64_t>(b->dims.syn_capacity, 1) + 2;
-        const uint64_t sizes[] = {cap * 8, cap * 8, cap * 12,
-                                  (uint64_t)kReorderDigits * kReorderMaxSegments * 4, (kReorderMaxSegments + 1) * 4ull,
-                                  kReorderStateWords * 4ull};
-        void** slots[] = {reinterpret_cast<void**>(&r.pairs[0]), reinterpret_cast<void**>(&r.pairs[1]),
-                          reinterpret_cast<void**>(&r.rec),      reinterpret_cast<void**>(&r.counts),
-                          reinterpret_cast<void**>(&r.seg_tomb), reinterpret_cast<void**>(&r.state)};
-        for (size_t i = 0; i < sizeof(sizes) / sizeof(sizes[0]); ++i) {
-            const hipError_t e = hipMalloc(slots[i], sizes[i]);
-            if (e != hipSuccess) {
-                *slots[i] = nullptr;
-                (void)hipGetLastError();
-                reorder_free(b);
-                set_err(std::string("reorder: hipMalloc(") + std::to_string(sizes[i]) + " B) of the scratch: " +
-                        hipGetErrorString(e));
-                return ABNN_ERR_OOM;
-            }
-        }
+        ST_TRY(b->pool.alloc_all({raw(&r.pairs[0], cap), raw(&r.pairs[1], cap), raw(&r.rec, cap * 3),
+                                  raw(&r.counts, (uint64_t)kReorderDigits * kReorderMaxSegments),
+                                  raw(&r.seg_tomb, kReorderMaxSegments + 1), raw(&r.state, kReorderStateWords)}));
         r.capacity = b->dims.syn_capacity;
     }
     return ABNN_OK;
@@ -1553,27 +1466,20 @@ abnn_status abnn_reorder(abnn_brain* b, const abnn_reorder_config* cfg, const ui
     REQUIRE(words == reorder_words(cfg, b->dims.n_syn), "abnn_reorder: words must equal abnn_reorder_words(cfg, n_syn)");
     ST_TRY(sync_all(b));
     // the device result and the staged perm live for this call only
+    DeviceTemp<uint64_t> res;
+    DeviceTemp<uint32_t> perm;
+    ST_TRY(res.alloc(words, false));  // no memset: launch_reorder fills the result
     const uint64_t n = b->dims.n_syn;
-    uint64_t* dev = nullptr;
-    uint32_t* perm_dev = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&dev), words * sizeof(uint64_t));
-    if (e == hipSuccess && perm_host) e = hipMalloc(reinterpret_cast<void**>(&perm_dev), std::max<uint64_t>(n, 1) * 4);
-    if (e != hipSuccess) {
-        if (dev) (void)hipFree(dev);
-        set_err(std::string("abnn_reorder: hipMalloc of the result: ") + hipGetErrorString(e));
-        return ABNN_ERR_OOM;
-    }
-    abnn_status st = ABNN_OK;
-    if (perm_host && n) e = hipMemcpyAsync(perm_dev, perm_host, n * 4, hipMemcpyHostToDevice, b->stream);
-    if (e == hipSuccess) st = reorder_launch(b, cfg, perm_dev, dev, b->stream);
-    if (e == hipSuccess && st == ABNN_OK)
-        e = hipMemcpyAsync(out_host, dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream);
-    const hipError_t e2 = hipStreamSynchronize(b->stream);
-    (void)hipFree(dev);
-    if (perm_dev) (void)hipFree(perm_dev);
+    if (perm_host) ST_TRY(perm.alloc(n, false));
+    const abnn_status st = [&]() -> abnn_status {  // the perm in, the reorder, the result out
+        if (perm_host && n) HIP_TRY(hipMemcpyAsync(perm.dev, perm_host, n * 4, hipMemcpyHostToDevice, b->stream));
+        ST_TRY(reorder_launch(b, cfg, perm.dev, res.dev, b->stream));
+        HIP_TRY(hipMemcpyAsync(out_host, res.dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
+        return ABNN_OK;
+    }();
+    const hipError_t e = hipStreamSynchronize(b->stream);  // before the two are freed, also after a failure
     ST_TRY(st);
     HIP_TRY(e);
-    HIP_TRY(e2);
     return ABNN_OK;
 }
 
@@ -1601,6 +1507,7 @@ abnn_status abnn_reorder_host(const abnn_reorder_config* cfg, uint64_t syn_offse
 // N_NRN, and the host mirrors as they were when the last capture was enqueued.
 struct abnn_snapshot {
     abnn_brain* b = nullptr;
+    DevicePool pool;                 // owns the buffers below
     SynArrays syn{};                 // lo, hi, dw of [0, n_syn); no src32 (restore rebuilds the mirror)
     uint64_t* last_fired = nullptr;  // [n_nrn]
     uint64_t* last_visited = nullptr;
@@ -1613,30 +1520,19 @@ struct abnn_snapshot {
 
 namespace {
 
-void snapshot_free(abnn_snapshot* s)
-{
-    if (!s) return;
-    if (s->b) (void)hipSetDevice(s->b->device);
-    void* ptrs[] = {s->syn.lo, s->syn.hi, s->syn.dw, s->last_fired, s->last_visited, s->scalars, s->grown};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    delete s;
-}
-
 abnn_status snapshot_alloc(abnn_snapshot* s)
 {
     const abnn_brain* b = s->b;
     const uint64_t cap = b->dims.syn_capacity + 2;  // whole 16-B pairs
-    ST_TRY(dalloc(&s->syn.lo, cap));
-    ST_TRY(dalloc(&s->syn.hi, cap));
-    ST_TRY(dalloc(&s->syn.dw, cap));
-    ST_TRY(dalloc(&s->last_fired, b->n_nrn));
-    ST_TRY(dalloc(&s->last_visited, b->n_nrn));
-    ST_TRY(dalloc(&s->scalars, 3));
+    std::vector<Slot> bufs = {zeroed(&s->syn.lo, cap),           zeroed(&s->syn.hi, cap),
+                              zeroed(&s->syn.dw, cap),           zeroed(&s->last_fired, b->n_nrn),
+                              zeroed(&s->last_visited, b->n_nrn), zeroed(&s->scalars, 3)};
     if (b->d.grown) {
         s->grown_slots = (uint64_t)b->params.compact_every * b->params.max_spikes;
-        ST_TRY(dalloc(&s->grown, s->grown_slots));
+        bufs.push_back(zeroed(&s->grown, s->grown_slots));
     }
+    ST_TRY(s->pool.alloc_all(bufs));
+    HIP_TRY(hipDeviceSynchronize());  // the buffers' zeros
     s->bytes = cap * 11 + b->n_nrn * 16 + 24 + s->grown_slots * 16;
     return ABNN_OK;
 }
@@ -1682,14 +1578,8 @@ abnn_status abnn_snapshot_create(abnn_brain* b, abnn_snapshot** out)
     s->b = b;
     const abnn_status st = snapshot_alloc(s);
     if (st != ABNN_OK) {
-        snapshot_free(s);
+        delete s;  // nothing half made: its pool frees the buffers
         return st;
-    }
-    const hipError_t e = hipDeviceSynchronize();  // the buffers' zeros
-    if (e != hipSuccess) {
-        snapshot_free(s);  // nothing half made
-        set_err(std::string("abnn_snapshot_create: hipDeviceSynchronize: ") + hipGetErrorString(e));
-        return ABNN_ERR_HIP;
     }
     *out = s;
     return ABNN_OK;
@@ -1700,7 +1590,7 @@ abnn_status abnn_snapshot_destroy(abnn_snapshot* s)
     if (!s) return ABNN_OK;
     (void)hipSetDevice(s->b->device);
     (void)hipDeviceSynchronize();  // an enqueued capture or diff may still use the buffers
-    snapshot_free(s);
+    delete s;  // its pool frees the buffers
     return ABNN_OK;
 }
 
@@ -1822,11 +1712,9 @@ abnn_status abnn_snapshot_diff(abnn_brain* b, const abnn_snapshot* then, const a
     ST_TRY(diff_sides_check(b, then, now));
     REQUIRE(words == diff_words(cfg), "abnn_snapshot_diff: words must equal abnn_snapshot_diff_words(cfg)");
     ST_TRY(sync_all(b));
-    if (!b->diff_out) ST_TRY(dalloc(&b->diff_out, ABNN_DIFF_HEADER_WORDS + ABNN_DIFF_MAX_BINS));
+    if (!b->diff_out) ST_TRY(b->pool.alloc(zeroed(&b->diff_out, ABNN_DIFF_HEADER_WORDS + ABNN_DIFF_MAX_BINS)));
     HIP_TRY(diff_launch(b, then, now, *cfg, scale, b->diff_out, b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->diff_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->diff_out, out_host, words);
 }
 
 abnn_status abnn_snapshot_diff_host(const abnn_diff_config* cfg, uint64_t n_nrn, const abnn_synapse* then,
@@ -1856,8 +1744,7 @@ abnn_status hops_check(abnn_brain* b, const abnn_hops_config* cfg)
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     HIP_TRY(hipSetDevice(b->device));
     // no memset: every step writes every word of the bitmap before it reads it
-    if (!b->hops_bitmap)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->hops_bitmap), hops_bitmap_words(b->n_nrn) * sizeof(uint32_t)));
+    if (!b->hops_bitmap) ST_TRY(b->pool.alloc(raw(&b->hops_bitmap, hops_bitmap_words(b->n_nrn))));
     return ABNN_OK;
 }
 
@@ -1898,11 +1785,9 @@ abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_
     ST_TRY(hops_check(b, cfg));
     REQUIRE(words == hops_words(cfg, b->n_nrn), "abnn_hops: words must equal abnn_hops_words(cfg, N_NRN)");
     ST_TRY(sync_all(b));
-    ST_TRY(grow(&b->hops_out, &b->hops_cap, words));
+    ST_TRY(b->pool.grow(&b->hops_out, &b->hops_cap, words));
     ST_TRY(hops_steps(b, cfg, b->hops_out, b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->hops_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->hops_out, out_host, words);
 }
 
 /* ---- spike recorder (spikes.hip) --------------------------- */
@@ -1912,9 +1797,7 @@ namespace {
 void spikes_free(abnn_brain* b)
 {
     SpikeRecorder& r = b->spikes;
-    void* ptrs[] = {r.words, r.passes, r.raster, r.counts};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
+    b->pool.release(&r.words, &r.passes, &r.raster, &r.counts);
     r = SpikeRecorder{};
 }
 
@@ -1935,14 +1818,10 @@ abnn_status abnn_spikes_start(abnn_brain* b, const abnn_spikes_config* cfg)
     r.cfg = *cfg;
     r.first = cfg->count ? cfg->first : 0u;
     r.n_counts = cfg->counts ? (cfg->count ? (uint64_t)cfg->count : b->n_nrn) : 0;
-    abnn_status st = dalloc(&r.words, kSpikeWords);
-    if (st == ABNN_OK) st = dalloc(&r.passes, cfg->pass_capacity);
-    if (st == ABNN_OK && cfg->raster_capacity) st = dalloc(&r.raster, cfg->raster_capacity);
-    if (st == ABNN_OK && r.n_counts) st = dalloc(&r.counts, r.n_counts);
-    if (st != ABNN_OK) {
-        spikes_free(b);
-        return st;
-    }
+    std::vector<Slot> bufs = {zeroed(&r.words, kSpikeWords), zeroed(&r.passes, cfg->pass_capacity)};
+    if (cfg->raster_capacity) bufs.push_back(zeroed(&r.raster, cfg->raster_capacity));
+    if (r.n_counts) bufs.push_back(zeroed(&r.counts, r.n_counts));
+    ST_TRY(b->pool.alloc_all(bufs));
     HIP_TRY(hipDeviceSynchronize());  // the buffers' zeros
     r.on = true;
     return ABNN_OK;
@@ -2066,28 +1945,12 @@ abnn_status corr_check(abnn_brain* b, const abnn_corr_config* cfg)
     REQUIRE(cfg->mode != ABNN_CORR_SYNAPSES || !b->records_invalid, kRecordsInvalid);
     HIP_TRY(hipSetDevice(b->device));
     CorrScratch& c = b->corr;
-    if (!c.map) {
-        // no memset: every word is written before it is read (launch_corr)
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.map), corr_map_words(b->n_nrn) * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cnt), b->n_nrn * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.off), b->n_nrn * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cur), b->n_nrn * sizeof(uint32_t)));
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.cursor), 2 * sizeof(uint32_t)));
-    }
-    if (!c.rows || c.raster_cap < b->spikes.cfg.raster_capacity) {
-        if (c.rows) (void)hipFree(c.rows);
-        c.rows = nullptr;
-        c.raster_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.rows), b->spikes.cfg.raster_capacity * sizeof(uint32_t)));
-        c.raster_cap = b->spikes.cfg.raster_capacity;
-    }
-    if (!c.tally || c.pass_cap < b->spikes.cfg.pass_capacity) {
-        if (c.tally) (void)hipFree(c.tally);
-        c.tally = nullptr;
-        c.pass_cap = 0;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&c.tally), (uint64_t)b->spikes.cfg.pass_capacity * sizeof(uint2)));
-        c.pass_cap = b->spikes.cfg.pass_capacity;
-    }
+    // no memset: every word is written before it is read (launch_corr)
+    if (!c.map)
+        ST_TRY(b->pool.alloc_all({raw(&c.map, corr_map_words(b->n_nrn)), raw(&c.cnt, b->n_nrn),
+                                  raw(&c.off, b->n_nrn), raw(&c.cur, b->n_nrn), raw(&c.cursor, 2)}));
+    ST_TRY(b->pool.grow(&c.rows, &c.raster_cap, b->spikes.cfg.raster_capacity, false));
+    ST_TRY(b->pool.grow(&c.tally, &c.pass_cap, b->spikes.cfg.pass_capacity, false));
     return ABNN_OK;
 }
 
@@ -2110,12 +1973,10 @@ abnn_status abnn_corr(abnn_brain* b, const abnn_corr_config* cfg, uint64_t* out_
     ST_TRY(corr_check(b, cfg));
     REQUIRE(words == corr_words(cfg), "abnn_corr: words must equal abnn_corr_words(cfg)");
     ST_TRY(sync_all(b));
-    ST_TRY(grow(&b->corr_out, &b->corr_cap, words));
+    ST_TRY(b->pool.grow(&b->corr_out, &b->corr_cap, words));
     HIP_TRY(launch_corr(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->spikes, b->corr, b->corr_out, (uint32_t)b->cus,
                         b->stream));
-    HIP_TRY(hipMemcpyAsync(out_host, b->corr_out, words * sizeof(uint64_t), hipMemcpyDeviceToHost, b->stream));
-    HIP_TRY(hipStreamSynchronize(b->stream));
-    return ABNN_OK;
+    return read_words(b, b->corr_out, out_host, words);
 }
 
 abnn_status abnn_corr_host(const abnn_corr_config* cfg, uint64_t n_nrn, const abnn_spike_pass* passes, uint64_t n_passes,
@@ -2384,6 +2245,7 @@ struct abnn_comm {
     abnn_comm_group* local = nullptr;  // in-process group (abnn_comm_create_local): no RCCL
     uint32_t world = 1, rank = 0;
     int device = 0;
+    DevicePool pool;            // owns the device buffers below
     char* gathered = nullptr;   // world exchange records, rank order
     uint64_t rec_bytes = 0;
     uint64_t* scratch = nullptr;  // visited-events all-reduce
@@ -2517,11 +2379,9 @@ abnn_status local_all_reduce_u64(abnn_comm* c, uint64_t* buf, uint64_t n, bool m
 {
     abnn_comm_group* g = c->local;
     if (c->red_n < n) {  // before the barrier: a failed allocation must not leave peers waiting in step 2
-        if (c->red_acc) (void)hipFree(c->red_acc);
-        if (c->red_in) (void)hipFree(c->red_in);
-        c->red_acc = c->red_in = nullptr;
+        c->pool.release(&c->red_acc, &c->red_in);
         c->red_n = 0;
-        if (dalloc(&c->red_acc, n) != ABNN_OK || dalloc(&c->red_in, n) != ABNN_OK) {
+        if (c->pool.alloc_all({zeroed(&c->red_acc, n), zeroed(&c->red_in, n)}) != ABNN_OK) {
             group_break(g, "rank " + std::to_string(c->rank) + " could not allocate the all-reduce buffers");
             return ABNN_ERR_OOM;
         }
@@ -2563,10 +2423,9 @@ static abnn_status merge_visits(abnn_brain* b, abnn_comm* c, hipStream_t s)
     if (!b->params.track_visits) return ABNN_OK;  // lastVisited is never written
     ST_TRY(ensure_visit_marks(b));
     if (c->visits_n != b->n_nrn) {
-        if (c->visits) HIP_TRY(hipFree(c->visits));
-        c->visits = nullptr;
+        c->pool.release(&c->visits);
         c->visits_n = 0;
-        ST_TRY(dalloc(&c->visits, b->n_nrn));
+        ST_TRY(c->pool.alloc(zeroed(&c->visits, b->n_nrn)));
         c->visits_n = b->n_nrn;
     }
     HIP_TRY(launch_visits_delta(b->d.last_visited, b->d.visit_mark, c->visits, b->n_nrn, s));
@@ -2614,7 +2473,7 @@ abnn_status abnn_comm_create(const void* id, uint32_t world, uint32_t rank, int 
     c->world = world;
     c->rank = rank;
     c->device = device;
-    if (dalloc(&c->scratch, 1) != ABNN_OK) {
+    if (c->pool.alloc(zeroed(&c->scratch, 1)) != ABNN_OK) {
         abnn_comm_destroy(c);
         return ABNN_ERR_OOM;
     }
@@ -2632,8 +2491,7 @@ abnn_status abnn_comm_destroy(abnn_comm* c)
         std::lock_guard<std::mutex> lk(c->local->m);
         c->local->ranks[c->rank] = nullptr;
     }
-    for (void* p : {(void*)c->gathered, (void*)c->scratch, (void*)c->visits, (void*)c->red_acc, (void*)c->red_in})
-        if (p) (void)hipFree(p);
+    c->pool.release_all();
     if (c->ev_ready) (void)hipEventDestroy(c->ev_ready);
     if (c->ev_done) (void)hipEventDestroy(c->ev_done);
     delete c;
@@ -2679,7 +2537,7 @@ abnn_status abnn_comm_create_local(abnn_comm_group* g, uint32_t rank, int device
     c->device = device;
     if (hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_done, hipEventDisableTiming) != hipSuccess ||
-        dalloc(&c->scratch, 1) != ABNN_OK) {
+        c->pool.alloc(zeroed(&c->scratch, 1)) != ABNN_OK) {
         c->local = nullptr;
         abnn_comm_destroy(c);
         set_err("abnn_comm_create_local: event or buffer allocation failed");
@@ -2708,9 +2566,8 @@ static abnn_status shard_traverse_passes(abnn_brain* b, abnn_comm* c, uint32_t p
 {
     const uint64_t rec = abnn_exchange_bytes(b);
     if (rec != c->rec_bytes) {  // the records' size follows the budget: sized on first use
-        if (c->gathered) HIP_TRY(hipFree(c->gathered));
-        c->gathered = nullptr;
-        ST_TRY(dalloc(&c->gathered, rec * c->world));
+        c->pool.release(&c->gathered);
+        ST_TRY(c->pool.alloc(zeroed(&c->gathered, rec * c->world)));
         c->rec_bytes = rec;
     }
     char* mine = c->gathered + rec * c->rank;
@@ -2863,6 +2720,9 @@ abnn_status abnn_debug_stream_pin(abnn_brain* b, uint32_t* pin_k)
     *pin_k = b->d.pin_k;
     return ABNN_OK;
 }
+
+// ... and the device allocations of pool.h that are live in this process.
+uint64_t abnn_debug_live_allocations(void) { return g_live_allocations.load(std::memory_order_relaxed); }
 
 abnn_status abnn_get_stats(abnn_brain* b, abnn_stats* out)
 {
@@ -3145,6 +3005,7 @@ abnn_status abnn_load_flat(abnn_brain* b, const char* path)
 struct abnn_engine {
     abnn_brain* b = nullptr;
     abnn_engine_config cfg{};
+    DevicePool pool;  // owns st's buffers, frames_dev and census_ring
     LearnState st{};
     float* frames_dev[2] = {};
     float* frames_host[2] = {};
@@ -3163,42 +3024,31 @@ struct abnn_engine {
     uint64_t census_words = 0, census_taken = 0;
     uint64_t* census_ring = nullptr;
     std::vector<uint64_t> census_steps;
+
+    ~abnn_engine()  // on the brain's device; the pool frees the device buffers
+    {
+        for (int k = 0; k < 2; ++k) {
+            if (frames_host[k]) (void)hipHostFree(frames_host[k]);
+            if (done[k]) (void)hipEventDestroy(done[k]);
+        }
+    }
 };
 
 namespace {
 
 constexpr uint64_t kSplitMixGamma = 0x9E3779B97F4A7C15ull;
 
-void engine_free(abnn_engine* e)
-{
-    if (!e) return;
-    (void)hipSetDevice(e->b->device);
-    void* ptrs[] = {e->st.sc, e->st.rate, e->st.filt, e->st.fir, e->st.smooth, e->st.spike_window,
-                    e->st.trace_out, e->st.trace_smooth, e->frames_dev[0], e->frames_dev[1], e->census_ring};
-    for (void* p : ptrs)
-        if (p) (void)hipFree(p);
-    for (int k = 0; k < 2; ++k) {
-        if (e->frames_host[k]) (void)hipHostFree(e->frames_host[k]);
-        if (e->done[k]) (void)hipEventDestroy(e->done[k]);
-    }
-    delete e;
-}
-
 abnn_status engine_alloc(abnn_engine* e)
 {
     LearnState& st = e->st;
     const uint64_t no = st.n_out, tp = st.trace_passes;
     const uint64_t frame_floats = tp * ((uint64_t)st.n_in + no);
-    ST_TRY(dalloc(&st.sc, 1));
-    ST_TRY(dalloc(&st.rate, no));
-    ST_TRY(dalloc(&st.filt, no));
-    ST_TRY(dalloc(&st.fir, st.use_fir ? (uint64_t)st.fir_size * no : 0));
-    ST_TRY(dalloc(&st.smooth, no));
-    ST_TRY(dalloc(&st.spike_window, no));
-    ST_TRY(dalloc(&st.trace_out, tp * no));
-    ST_TRY(dalloc(&st.trace_smooth, tp * no));
+    ST_TRY(e->pool.alloc_all(
+        {zeroed(&st.sc, 1), zeroed(&st.rate, no), zeroed(&st.filt, no), zeroed(&st.smooth, no),
+         zeroed(&st.fir, st.use_fir ? (uint64_t)st.fir_size * no : 0), zeroed(&st.spike_window, no),
+         zeroed(&st.trace_out, tp * no), zeroed(&st.trace_smooth, tp * no),
+         zeroed(&e->frames_dev[0], frame_floats), zeroed(&e->frames_dev[1], frame_floats)}));
     for (int k = 0; k < 2; ++k) {
-        ST_TRY(dalloc(&e->frames_dev[k], frame_floats));
         HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&e->frames_host[k]), std::max<uint64_t>(frame_floats, 1) * 4,
                               hipHostMallocDefault));
         HIP_TRY(hipEventCreateWithFlags(&e->done[k], hipEventDisableTiming));
@@ -3265,7 +3115,7 @@ abnn_status abnn_engine_create(abnn_brain* b, const abnn_engine_config* cfg, abn
     st.filt_a = cfg->dt_sec / (cfg->filter_tau + cfg->dt_sec);  // rate-filter.h:30
     const abnn_status s = engine_alloc(e);
     if (s != ABNN_OK) {
-        engine_free(e);
+        delete e;
         return s;
     }
     *out = e;
@@ -3277,7 +3127,7 @@ abnn_status abnn_engine_destroy(abnn_engine* e)
     REQUIRE(e, "null argument");
     (void)hipSetDevice(e->b->device);
     (void)hipDeviceSynchronize();
-    engine_free(e);
+    delete e;
     return ABNN_OK;
 }
 
@@ -3399,14 +3249,13 @@ abnn_status abnn_engine_set_census(abnn_engine* e, const abnn_census_config* cfg
         REQUIRE(every >= 1 && capacity >= 1, "abnn_engine_set_census: every and capacity must be at least 1");
     }
     ST_TRY(sync_all(e->b));  // censuses already enqueued write the ring
-    if (e->census_ring) (void)hipFree(e->census_ring);
-    e->census_ring = nullptr;
+    e->pool.release(&e->census_ring);
     e->census_on = false;
     e->census_taken = 0;
     e->census_steps.clear();
     if (!cfg) return ABNN_OK;
     const uint64_t words = abnn_census_words(cfg);
-    ST_TRY(dalloc(&e->census_ring, words * capacity));
+    ST_TRY(e->pool.alloc(zeroed(&e->census_ring, words * capacity)));
     e->census_steps.assign(capacity, 0);
     e->census_cfg = *cfg;
     e->census_scale = scale;

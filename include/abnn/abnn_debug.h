@@ -61,6 +61,13 @@ abnn_status abnn_debug_raw_wave_clock(const void* workspace, uint64_t workspace_
  * buf holds world x bytes, this rank's record at rank x bytes). */
 abnn_status abnn_debug_comm_allgather(abnn_comm* c, void* buf, uint64_t bytes, uint32_t count, void* stream);
 
+/* Device allocations the library made (for its handles: brains, snapshots,
+ * engines, communicators, and inside its calls) and has not freed yet, in the
+ * whole process.  Every destroy brings it back to what it was before the
+ * create; a caller's workspace (abnn_launch_traversal) is not the library's and
+ * is not counted.  Not synchronous, touches no device. */
+uint64_t abnn_debug_live_allocations(void);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

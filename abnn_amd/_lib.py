@@ -247,6 +247,25 @@ class HopsConfig(C.Structure):
     ]
 
 
+PROP_REVERSE, PROP_FIRE_P, PROP_WEIGHT = 1, 2, 4
+PROP_HEADER_WORDS = 8
+PROP_TRACE_WORDS = 8
+PROP_MAX_STEPS = 4096
+
+
+class PropagateConfig(C.Structure):
+    """abnn_propagate_config -- the in- and out-range (count 0 = every neuron), the flags and the weight bounds of a
+    propagation."""
+
+    _fields_ = [
+        ("in_first", C.c_uint32), ("in_count", C.c_uint32),
+        ("out_first", C.c_uint32), ("out_count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("reserved", C.c_uint32 * 5),
+    ]
+
+
 GRAPH_MAX_BLOCKS = 16
 GRAPH_KEY = 0xD1B54A32D192ED03
 TOPO_DENSE, TOPO_RANDOM, TOPO_RING = 0, 1, 2
@@ -412,6 +431,13 @@ SIGNATURES = [
     ("abnn_hops_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _VP]),
     ("abnn_hops_step_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), C.c_uint32, _VP, _VP]),
     ("abnn_hops", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _U64]),
+    ("abnn_propagate_words", C.c_uint64, [C.POINTER(PropagateConfig), _U64]),
+    ("abnn_propagate_enqueue", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _VP]),
+    ("abnn_propagate", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _U64]),
+    ("abnn_propagate_rescale_enqueue", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _VP, _VP]),
+    ("abnn_propagate_iterate_enqueue", C.c_int, [_VP, C.POINTER(PropagateConfig), _U32, _VP, _VP, _VP, _VP]),
+    ("abnn_propagate_host", C.c_int, [C.POINTER(PropagateConfig), _U64, _F, _VP, _U64, _VP, _VP]),
+    ("abnn_propagate_rescale_host", C.c_int, [C.POINTER(PropagateConfig), _U64, _VP, _VP, _VP]),
     ("abnn_spikes_start", C.c_int, [_VP, C.POINTER(SpikesConfig)]),
     ("abnn_spikes_stop", C.c_int, [_VP]),
     ("abnn_spikes_clear", C.c_int, [_VP, C.c_int]),
@@ -500,7 +526,9 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_snapshot_diff_enqueue", "abnn_snapshot_diff", "abnn_snapshot_diff_host",
                    "abnn_spikes_load", "abnn_corr_words", "abnn_corr_enqueue", "abnn_corr", "abnn_corr_host",
                    "abnn_reorder_words", "abnn_reorder_enqueue", "abnn_reorder", "abnn_reorder_release",
-                   "abnn_reorder_host")
+                   "abnn_reorder_host",
+                   "abnn_propagate_words", "abnn_propagate_enqueue", "abnn_propagate", "abnn_propagate_rescale_enqueue",
+                   "abnn_propagate_iterate_enqueue", "abnn_propagate_host", "abnn_propagate_rescale_host")
 
 _lib = None
 
@@ -532,6 +560,7 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_raw_fused_active", C.c_int, []),
     ("abnn_debug_raw_wave_clock", C.c_int, [_VP, C.c_uint64, _U32, _U32, C.POINTER(C.c_uint64), C.c_uint64, _VP]),
     ("abnn_debug_live_allocations", C.c_uint64, []),
+    ("abnn_debug_set_propagate_path", C.c_int, [_VP, C.c_int]),
 ]
 
 

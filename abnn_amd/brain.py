@@ -20,6 +20,7 @@ from . import corr as _corr
 from . import degree as _degree
 from . import edit as _edit
 from . import hops as _hops
+from . import propagate as _propagate
 from . import reorder as _reorder
 from . import select as _select
 from . import spikes as _spikes
@@ -384,6 +385,87 @@ class Brain:
         device memory at ``out_ptr``: the sharded caller's path, which merges
         the ranks' planes (hops.merge_planes) between two steps."""
         call("abnn_hops_step_enqueue", self._h, C.byref(cfg), int(step), int(out_ptr), _stream_ptr(stream))
+
+    def propagate(self, x, inputs=None, outputs=None, reverse: bool = False, fire_p: bool = False, weights=None) -> dict:
+        """Signal propagation on the device (abnn_propagate):
+        y[kout] += c(w) * x[kin] over this handle's records, in integers.
+        ``x`` holds N_NRN int32 (propagate.to_fixed); ``inputs`` / ``outputs``
+        are the (first, count) ranges x is read from and y is summed over
+        (None: every neuron); ``reverse`` is the transpose, ``fire_p`` takes
+        the fire probability (w*w)*base_scale for c, ``weights`` = (w_lo,
+        w_hi) follows only records with w_lo <= w < w_hi; the rule is in
+        abnn.h.  Returns records, tombstones, followed, skipped, nnz,
+        sum_abs_x and ``y`` (np.int64, 8 fractional bits more than x)
+        (propagate.decode)."""
+        cfg = _propagate.config(inputs, outputs, reverse, fire_p, weights)
+        n_nrn = self.n_neuron()
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        if x.shape != (n_nrn,):
+            raise ValueError("propagate: x must hold N_NRN entries")
+        words = int(self._lib.abnn_propagate_words(C.byref(cfg), n_nrn))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_propagate", self._h, C.byref(cfg), _ptr(x), _ptr(out), words)  # an invalid config fails here
+        return _propagate.decode(out, cfg, n_nrn)
+
+    def propagate_enqueue(self, cfg: _lib.PropagateConfig, x_ptr: int, out_ptr: int, stream=None) -> None:
+        """Enqueue a propagation of the device plane at ``x_ptr`` (N_NRN
+        int32, 16-byte aligned) into device memory at ``out_ptr``
+        (abnn_propagate_words(cfg, N_NRN) u64) on ``stream``; nothing
+        synchronises after the handle's first propagation.  Decode with
+        propagate.decode."""
+        call("abnn_propagate_enqueue", self._h, C.byref(cfg), int(x_ptr), int(out_ptr), _stream_ptr(stream))
+
+    def propagate_rescale_enqueue(self, cfg: _lib.PropagateConfig, out_ptr: int, x_ptr: int, row_ptr: Optional[int] = None,
+                                  stream=None) -> None:
+        """Enqueue the rescale of the result at ``out_ptr`` into the plane at
+        ``x_ptr`` over the out-range, with its trace row (8 u64) at ``row_ptr``
+        (None: no row)."""
+        call("abnn_propagate_rescale_enqueue", self._h, C.byref(cfg), int(out_ptr), int(x_ptr),
+             int(row_ptr) if row_ptr else None, _stream_ptr(stream))
+
+    def propagate_iterate_enqueue(self, cfg: _lib.PropagateConfig, steps: int, x_ptr: int, work_ptr: int, trace_ptr: int,
+                                  stream=None) -> None:
+        """Enqueue ``steps`` times propagate and rescale (abnn_propagate_iterate_enqueue):
+        the plane at ``x_ptr`` ends as the last rescaled one, ``trace_ptr``
+        holds steps x 8 u64 (propagate.branching reads them)."""
+        call("abnn_propagate_iterate_enqueue", self._h, C.byref(cfg), int(steps), int(x_ptr), int(work_ptr),
+             int(trace_ptr), _stream_ptr(stream))
+
+    def branching(self, steps: int = 16, neurons=None, fire_p: bool = True, reverse: bool = False, weights=None,
+                  x0=None) -> dict:
+        """The branching ratio on the device: ``steps`` power iterations of
+        the fire-probability matrix (``fire_p``; else of the weights)
+        restricted to ``neurons`` = (first, count) (None: every neuron), from
+        ``x0`` (N_NRN int32; None: propagate.ONE >> 1 on every neuron of the
+        range), all enqueued on one stream with one synchronise at the end.
+        Returns propagate.branching of the trace (``ratio``, ``estimates``,
+        ...) and ``x``, the last rescaled plane (np.int32, N_NRN): the
+        influence vector (with ``reverse``, of the transpose)."""
+        import torch
+
+        dev = torch.device("cuda", self.device)
+        n_nrn = self.n_neuron()
+        cfg = _propagate.config(neurons, neurons, reverse, fire_p, weights)
+        words = _propagate.n_words(cfg, n_nrn)
+        if not words:
+            raise ValueError("branching: invalid neuron range or weight bounds")
+        if x0 is None:
+            first, count = _propagate.ranges(cfg, n_nrn)[:2]
+            x0 = np.zeros(n_nrn, dtype=np.int32)
+            x0[first:first + count] = _propagate.ONE >> 1
+        x0 = np.ascontiguousarray(x0, dtype=np.int32)
+        if x0.shape != (n_nrn,):
+            raise ValueError("branching: x0 must hold N_NRN entries")
+        with torch.cuda.device(dev):
+            x = torch.from_numpy(x0).to(dev)
+            work = torch.zeros(words, dtype=torch.int64, device=dev)
+            trace = torch.zeros(int(steps) * _lib.PROP_TRACE_WORDS, dtype=torch.int64, device=dev)
+            stream = torch.cuda.current_stream(dev)
+            self.propagate_iterate_enqueue(cfg, steps, x.data_ptr(), work.data_ptr(), trace.data_ptr(), stream)
+            stream.synchronize()
+        out = _propagate.branching(trace.cpu().numpy().view(np.uint64))
+        out["x"] = x.cpu().numpy()
+        return out
 
     # ---- spike recorder (abnn_spikes_*, DESIGN.md §9) -------------------------------------------
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:

@@ -18,6 +18,7 @@
 * ``build_corr_host_test()`` : g++ -fsanitize -> tests/cpp/corr_host_test (the correlograms' host rule alone, CPU only)
 * ``build_reorder_test()``   : g++ -> tests/cpp/reorder_test (the record reorder's C++ mirror vs abnn_reorder_host)
 * ``build_reorder_host_test()`` : g++ -fsanitize -> tests/cpp/reorder_host_test (the reorder's host rule alone, CPU only)
+* ``build_propagate_test()`` : g++ -> tests/cpp/propagate_test (the propagation's C++ mirrors vs abnn_propagate_host)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -35,12 +36,14 @@ HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip")
                os.path.join(CSRC, "learn.hip"), os.path.join(CSRC, "census.hip"), os.path.join(CSRC, "spikes.hip"),
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
                os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
-               os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip"), os.path.join(CSRC, "reorder.hip")]
+               os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip"), os.path.join(CSRC, "reorder.hip"),
+               os.path.join(CSRC, "propagate.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
                           os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "pool.h"),
+                          os.path.join(CSRC, "propagate.h"), os.path.join(CSRC, "runs.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -81,6 +84,8 @@ REORDER_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "reorder_test.cpp")
 REORDER_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "reorder_test")
 REORDER_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "reorder_host_test.cpp")
 REORDER_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "reorder_host_test")
+PROPAGATE_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "propagate_test.cpp")
+PROPAGATE_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "propagate_test")
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -416,6 +421,21 @@ def build_reorder_host_test(force: bool = False, out: str | None = None) -> str 
     return target
 
 
+def build_propagate_test(force: bool = False) -> str | None:
+    """Test program of the signal propagation's C++ mirrors (Brain::propagate /
+    branching, PropagateView against abnn_propagate_host on the generated graph;
+    the enqueued iteration on device planes)."""
+    if not os.path.exists(PROPAGATE_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [PROPAGATE_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(PROPAGATE_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", PROPAGATE_TEST_BIN, PROPAGATE_TEST_SRC, "-L", PKG, "-labnn_hip", "-ldl",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return PROPAGATE_TEST_BIN
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -445,6 +465,7 @@ def build_all(force: bool = False) -> None:
     build_snapshot_test(force)
     build_corr_test(force)
     build_reorder_test(force)
+    build_propagate_test(force)
     build_learn_bench(force)
 
 

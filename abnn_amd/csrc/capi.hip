@@ -28,6 +28,7 @@
 #include "spikes.h"
 #include "corr.h"
 #include "reorder.h"
+#include "propagate.h"
 #include "pool.h"
 
 using namespace abnn;
@@ -132,6 +133,11 @@ struct abnn_brain {
     ReorderScratch reorder;          // abnn_reorder_*: the pair buffers and the records' packed copy for syn_capacity (its first call)
     uint32_t reorder_blocks = 0;     // ... the most workgroups of its launches (4 per CU; ABNN_REORDER_BLOCKS)
     bool reorder_skip = true;        // ... leaving out the radix passes of a constant digit (ABNN_REORDER_SKIP=0: all four)
+    PropScratch prop;                // abnn_propagate_*: the non-zero map and the rescale's words (its first call)
+    uint32_t prop_path = 0;          // ... the forward instance: 0 the device chooses, 1 sparse, 2 dense (abnn_debug_set_propagate_path)
+    int32_t* prop_x = nullptr;       // abnn_propagate's staged x plane, N_NRN int32 (its first call)
+    uint64_t* prop_out = nullptr;    // abnn_propagate's device result, grown to the largest one asked
+    uint64_t prop_cap = 0;
     int cus = 256, per_cu = 1;     // gate partition inputs (configure)
     uint64_t pass_host = 0;        // mirror of pass_index (structural-update schedule)
     uint64_t rot = 0;              // passes run by this handle: the bitmap buffers' rotation (never reset)
@@ -1788,6 +1794,123 @@ abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_
     ST_TRY(b->pool.grow(&b->hops_out, &b->hops_cap, words));
     ST_TRY(hops_steps(b, cfg, b->hops_out, b->stream));
     return read_words(b, b->hops_out, out_host, words);
+}
+
+/* ---- signal propagation (propagate.hip) ----------------------- */
+
+uint64_t abnn_propagate_words(const abnn_propagate_config* cfg, uint64_t n_nrn) { return propagate_words(cfg, n_nrn); }
+
+namespace {
+
+constexpr const char* kPropConfig =
+    "propagate: no unknown flags, reserved 0, a count of 0 only with first 0, both ranges inside N_NRN, "
+    "w_lo / w_hi +0 without WEIGHT, with it no NaN bound and w_lo < w_hi";
+
+// The checks of a propagation on handle b, then its scratch (the first call
+// allocates it: that one may synchronise the device).
+abnn_status propagate_check(abnn_brain* b, const abnn_propagate_config* cfg)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE(propagate_config_ok(cfg, b->n_nrn, nullptr), kPropConfig);
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // no memset: k_prop_map writes every word of the map, the rescale zeroes its words in stream order
+    if (!b->prop.map)
+        ST_TRY(b->pool.alloc_all({raw(&b->prop.map, (b->n_nrn + 31) / 32), raw(&b->prop.red, 2)}));
+    return ABNN_OK;
+}
+
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+abnn_status propagate_launch(abnn_brain* b, const abnn_propagate_config* cfg, const int32_t* x_dev, uint64_t* out_dev,
+                             hipStream_t s)
+{
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_propagate(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, b->kp.base_scale, x_dev, out_dev, b->prop, b->prop_path,
+                             (uint32_t)b->cus, s));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_propagate_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, const int32_t* x_dev, uint64_t* out_dev,
+                                   void* stream)
+{
+    REQUIRE(b && cfg && x_dev && out_dev, "null argument");
+    REQUIRE(aligned(x_dev, 16) && aligned(out_dev, 8), "propagate: x_dev must be 16-byte and out_dev 8-byte aligned");
+    ST_TRY(propagate_check(b, cfg));
+    return propagate_launch(b, cfg, x_dev, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_propagate(abnn_brain* b, const abnn_propagate_config* cfg, const int32_t* x_host, uint64_t* out_host,
+                           uint64_t words)
+{
+    REQUIRE(b && cfg && x_host && out_host, "null argument");
+    ST_TRY(propagate_check(b, cfg));
+    REQUIRE(words == propagate_words(cfg, b->n_nrn), "abnn_propagate: words must equal abnn_propagate_words(cfg, N_NRN)");
+    ST_TRY(sync_all(b));
+    if (!b->prop_x) ST_TRY(b->pool.alloc(raw(&b->prop_x, b->n_nrn)));
+    ST_TRY(b->pool.grow(&b->prop_out, &b->prop_cap, words, false));
+    HIP_TRY(hipMemcpyAsync(b->prop_x, x_host, b->n_nrn * sizeof(int32_t), hipMemcpyHostToDevice, b->stream));
+    ST_TRY(propagate_launch(b, cfg, b->prop_x, b->prop_out, b->stream));
+    return read_words(b, b->prop_out, out_host, words);
+}
+
+abnn_status abnn_propagate_rescale_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, const uint64_t* out_dev,
+                                           int32_t* x_dev, uint64_t* trace_row_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev && x_dev, "null argument");
+    REQUIRE(aligned(x_dev, 16) && aligned(out_dev, 8) && aligned(trace_row_dev, 8),
+            "propagate: x_dev must be 16-byte, out_dev and trace_row_dev 8-byte aligned");
+    ST_TRY(propagate_check(b, cfg));
+    HIP_TRY(launch_propagate_rescale(*cfg, b->n_nrn, out_dev, x_dev, trace_row_dev, b->prop, (uint32_t)b->cus,
+                                     pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_propagate_iterate_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, uint32_t steps, int32_t* x_dev,
+                                           uint64_t* work_dev, uint64_t* trace_dev, void* stream)
+{
+    REQUIRE(b && cfg && x_dev && work_dev && trace_dev, "null argument");
+    REQUIRE(aligned(x_dev, 16) && aligned(work_dev, 8) && aligned(trace_dev, 8),
+            "propagate: x_dev must be 16-byte, work_dev and trace_dev 8-byte aligned");
+    ST_TRY(propagate_check(b, cfg));
+    REQUIRE(steps >= 1 && steps <= kPropMaxSteps, "propagate: steps must be 1 .. 4096");
+    REQUIRE(propagate_ranges_equal(*cfg), "propagate: iterate needs the in-range and the out-range to be the same");
+    hipStream_t s = pick(b, stream);
+    for (uint32_t k = 0; k < steps; ++k) {
+        ST_TRY(propagate_launch(b, cfg, x_dev, work_dev, s));
+        HIP_TRY(launch_propagate_rescale(*cfg, b->n_nrn, work_dev, x_dev, trace_dev + (uint64_t)k * ABNN_PROP_TRACE_WORDS,
+                                         b->prop, (uint32_t)b->cus, s));
+    }
+    return ABNN_OK;
+}
+
+abnn_status abnn_propagate_host(const abnn_propagate_config* cfg, uint64_t n_nrn, float base_scale, const abnn_synapse* syn,
+                                uint64_t n_syn, const int32_t* x, uint64_t* out)
+{
+    REQUIRE(cfg && x && out && (syn || n_syn == 0), "null argument");
+    REQUIRE(propagate_config_ok(cfg, n_nrn, nullptr), kPropConfig);
+    propagate_host(*cfg, n_nrn, base_scale, syn, n_syn, x, out);
+    return ABNN_OK;
+}
+
+abnn_status abnn_propagate_rescale_host(const abnn_propagate_config* cfg, uint64_t n_nrn, const uint64_t* out, int32_t* x,
+                                        uint64_t* trace_row)
+{
+    REQUIRE(cfg && out && x, "null argument");
+    REQUIRE(propagate_config_ok(cfg, n_nrn, nullptr), kPropConfig);
+    propagate_rescale_host(*cfg, n_nrn, out, x, trace_row);
+    return ABNN_OK;
+}
+
+// Diagnostics (not part of abnn.h): pin the forward instance of the handle's propagations.
+abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(path >= 0 && path <= 2, "abnn_debug_set_propagate_path: 0 auto, 1 sparse, 2 dense");
+    b->prop_path = (uint32_t)path;
+    return ABNN_OK;
 }
 
 /* ---- spike recorder (spikes.hip) --------------------------- */

@@ -534,6 +534,70 @@ class ShardedBrain:
         got[0] = int(records.item())
         return _hops.decode(got, cfg, n_nrn)
 
+    def _propagate_merged(self, cfg, x, out, stream):
+        """One collective step: this rank's propagation of the device plane
+        ``x`` into ``out``, then words 0..3 and y summed over the ranks (exact:
+        int64 sums that wrap as the device's do).  Words 4 and 5 describe the
+        one x every rank reads and stay the rank's own."""
+        self.brain.propagate_enqueue(cfg, x.data_ptr(), out.data_ptr(), stream)
+        keep = out[4:6].clone()
+        self.comm.all_reduce_sum(out)  # words 6 / 7 are zeros on every rank
+        out[4:6] = keep
+
+    def propagate(self, x, inputs=None, outputs=None, reverse: bool = False, fire_p: bool = False, weights=None) -> dict:
+        """Brain.propagate over every shard's records (collective: every rank
+        calls it at the same point with the same ``x`` and gets the whole
+        graph's result): the local pass, then the record counts and y summed
+        (all_reduce_sum), which is propagate.merge."""
+        from . import propagate as _propagate
+
+        torch, dev = self._torch, self.xchg.device
+        cfg = _propagate.config(inputs, outputs, reverse, fire_p, weights)
+        n_nrn = self.brain.n_neuron()
+        words = _propagate.n_words(cfg, n_nrn)
+        x = np.ascontiguousarray(x, dtype=np.int32)
+        if not words or x.shape != (n_nrn,):
+            raise ValueError("propagate: invalid config or x")
+        t_x = torch.from_numpy(x).to(dev)
+        out = torch.zeros(words, dtype=torch.int64, device=dev)
+        self._propagate_merged(cfg, t_x, out, torch.cuda.current_stream(dev))
+        return _propagate.decode(out.cpu().numpy().view(np.uint64), cfg, n_nrn)
+
+    def branching(self, steps: int = 16, neurons=None, fire_p: bool = True, reverse: bool = False, weights=None,
+                  x0=None) -> dict:
+        """Brain.branching over every shard's records (collective).  Every
+        rank holds some of the records, so this drives the steps itself: each
+        rank propagates its own records, the results are summed over the ranks
+        and the rescale follows the merge (the way :meth:`hops` merges between
+        two steps), so every rank holds the same x and the same trace."""
+        from . import propagate as _propagate
+
+        torch, dev = self._torch, self.xchg.device
+        cfg = _propagate.config(neurons, neurons, reverse, fire_p, weights)
+        n_nrn = self.brain.n_neuron()
+        words = _propagate.n_words(cfg, n_nrn)
+        if not words or not 1 <= int(steps) <= _propagate.PROP_MAX_STEPS:
+            raise ValueError("branching: invalid neuron range, weight bounds or steps")
+        if x0 is None:
+            first, count = _propagate.ranges(cfg, n_nrn)[:2]
+            x0 = np.zeros(n_nrn, dtype=np.int32)
+            x0[first:first + count] = _propagate.ONE >> 1
+        x0 = np.ascontiguousarray(x0, dtype=np.int32)
+        if x0.shape != (n_nrn,):
+            raise ValueError("branching: x0 must hold N_NRN entries")
+        x = torch.from_numpy(x0).to(dev)
+        out = torch.zeros(words, dtype=torch.int64, device=dev)
+        trace = torch.zeros(int(steps) * _propagate.PROP_TRACE_WORDS, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        for k in range(int(steps)):
+            self._propagate_merged(cfg, x, out, stream)
+            self.brain.propagate_rescale_enqueue(cfg, out.data_ptr(), x.data_ptr(),
+                                                 trace.data_ptr() + 8 * _propagate.PROP_TRACE_WORDS * k, stream)
+        stream.synchronize()
+        res = _propagate.branching(trace.cpu().numpy().view(np.uint64))
+        res["x"] = x.cpu().numpy()
+        return res
+
     def record_spikes(self, raster: int, passes: int, neurons=None, counts: bool = False) -> None:
         """Brain.record_spikes on the local handle.  No collective: every
         rank's spike list is the merged global one, so any rank's recorder

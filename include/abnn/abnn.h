@@ -904,6 +904,99 @@ abnn_status abnn_hops_step_enqueue(abnn_brain* b, const abnn_hops_config* cfg, u
  * N_NRN)).  Its device result stays with the handle until abnn_brain_destroy. */
 abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_host, uint64_t words);
 
+/* ---- signal propagation: W.x and the branching ratio ----------
+ * The handle's local records [0, n_syn) used as the sparse matrix they are: one
+ * streaming pass y[kout] += c(w) * x[kin] on the device, in integers, without
+ * moving the records to the host.  x is a plane of N_NRN int32: a fixed-point
+ * activity whose scale is the caller's (abnn_amd/propagate.py uses 1 << 30).
+ * For a record (src, dst, w): kin = src, kout = dst; with ABNN_PROP_REVERSE kin =
+ * dst, kout = src (the transpose).  In = [in_first, in_first + in_count), Out =
+ * [out_first, out_first + M) likewise (a count of 0: every neuron).
+ * Followed records.  Record k < n_syn is FOLLOWED when it is live (dst !=
+ * 0xFFFFFFFF), kin - in_first < in_count and kout - out_first < M as u32
+ * comparisons, with ABNN_PROP_WEIGHT w >= w_lo && w < w_hi (abnn_select's rule:
+ * NaN never matches), and x[kin] != 0.  Records at or past n_syn are never read.
+ * Term.  c = w, with ABNN_PROP_FIRE_P c = (w*w)*base_scale (the handle's
+ * base_scale; two fp32 operations in this order): the probability that an event
+ * on the record fires.  c is SUMMABLE iff fabsf(c) < 128.0f; then q =
+ * (int32_t)(c * 16777216.0f) (the degree census's term), term = ((int64_t)q *
+ * (int64_t)x[kin]) >> 16 (arithmetic: a floor) and y[kout - out_first] += term
+ * modulo 2^64.  y carries 8 fractional bits more than x: its value is
+ * (int64_t)y / 256 in x's units.  A followed record that is not summable adds
+ * nothing and counts in word 3.
+ * Result: ABNN_PROP_HEADER_WORDS + M u64 words:
+ *   0 records scanned (= n_syn)   1 tombstones among them
+ *   2 records followed            3 followed records that are not summable
+ *   4 non-zero x in In            5 the sum of |x| over In           6, 7 zero
+ *   8... y, word j belongs to neuron out_first + j.
+ * Every word is an integer sum, so the result is the same for any grid, order
+ * and path (abnn_amd/propagate.py restates it in numpy).  A tombstone carries
+ * src = dst = 0xFFFFFFFF (every writer of records keeps the two together): the
+ * sparse forward path counts word 1 from the src stream.
+ * Rescale.  A result's y into the next x over Out: Mx = max |y_j| as u64
+ * (INT64_MIN counts as 2^63), L = the bit length of Mx, e = 30 - L, x[out_first
+ * + j] = (int32_t)(e >= 0 ? y_j << e : y_j >> -e) (arithmetic), so that 2^29 <=
+ * max |x| <= 2^30; Mx == 0 gives x = 0 and e = 0.  x outside Out is not touched.
+ * Its trace row, 8 u64: {word 4, word 5, the sum of |y| mod 2^64, Mx,
+ * (uint64_t)(int64_t)e, word 2, word 3, 0}.  (sum |y| / 256) / word 5 estimates
+ * the step's eigenvalue: for non-negative c and x it converges, iterated, to the
+ * spectral radius of the operator restricted to Out x Out -- with FIRE_P the
+ * branching ratio.
+ * Iterate.  `steps` (1 .. ABNN_PROP_MAX_STEPS) times propagate x -> work, rescale
+ * work -> x, one trace row per step; In and Out must be the same range.
+ * Shards.  A shard propagates its own records; the sum of the shards' results,
+ * word by word except words 4 and 5 (every shard reads the same x), is the
+ * unsharded result, and the rescale follows the sum.
+ * Scratch.  The non-zero map (N_NRN bits) and the rescale's two words stay with
+ * the handle: the FIRST propagate call on a handle allocates them and may
+ * synchronise the device; abnn_brain_destroy frees them.  Two propagations of
+ * one handle enqueued on different streams must be ordered by the caller.      */
+#define ABNN_PROP_REVERSE   1u   /* the transpose: kin = dst, kout = src */
+#define ABNN_PROP_FIRE_P    2u   /* c = (w*w)*base_scale, not w */
+#define ABNN_PROP_WEIGHT    4u   /* follow a record only if w_lo <= w && w < w_hi */
+#define ABNN_PROP_HEADER_WORDS 8
+#define ABNN_PROP_TRACE_WORDS  8
+#define ABNN_PROP_MAX_STEPS 4096u
+typedef struct abnn_propagate_config {   /* 48 bytes */
+    uint32_t in_first, in_count;     /* In; count 0 = every neuron (first must be 0) */
+    uint32_t out_first, out_count;   /* Out, likewise */
+    uint32_t flags;
+    float    w_lo, w_hi;             /* as abnn_select_config: +0.0f unless WEIGHT */
+    uint32_t reserved[5];            /* 0 */
+} abnn_propagate_config;
+/* The result's words for a brain of n_nrn neurons, or 0 for an invalid config:
+ * null, unknown flag bits, a reserved word that is not 0, a count of 0 with a
+ * first that is not, a range that ends above n_nrn, a non-zero w_lo or w_hi
+ * without WEIGHT, a NaN bound or w_lo >= w_hi with it, n_nrn == 0 or >= 2^32.  */
+uint64_t    abnn_propagate_words(const abnn_propagate_config* cfg, uint64_t n_nrn);
+/* Enqueue only: zeroes and fills out_dev (DEVICE memory, 8-byte aligned,
+ * abnn_propagate_words(cfg, N_NRN) u64) from x_dev (DEVICE memory, 16-byte
+ * aligned, N_NRN int32) in stream order on `stream`; nothing synchronises after
+ * the handle's first propagate call, so it can sit between passes and between
+ * abnn_engine_run calls.  ABNN_ERR_INVALID: a null argument, a misaligned
+ * plane, a config that is invalid for the handle's N_NRN, a handle whose
+ * records are invalid.  n_syn == 0 is valid: y is zero.                        */
+abnn_status abnn_propagate_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, const int32_t* x_dev, uint64_t* out_dev, void* stream);
+/* Synchronous convenience with host planes: x_host holds N_NRN int32, out_host
+ * `words` u64 (== abnn_propagate_words(cfg, N_NRN)).  Its device planes stay
+ * with the handle until abnn_brain_destroy.                                    */
+abnn_status abnn_propagate(abnn_brain* b, const abnn_propagate_config* cfg, const int32_t* x_host, uint64_t* out_host, uint64_t words);
+/* Enqueue only: the rescale of the result out_dev into x_dev over Out and, when
+ * trace_row_dev is not null, its trace row (DEVICE memory, 8 u64).             */
+abnn_status abnn_propagate_rescale_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, const uint64_t* out_dev, int32_t* x_dev, uint64_t* trace_row_dev, void* stream);
+/* Enqueue only: `steps` times propagate and rescale; x_dev ends as the last
+ * rescaled plane, work_dev (abnn_propagate_words u64) as the last result,
+ * trace_dev (steps x 8 u64) holds one row per step.  Also ABNN_ERR_INVALID for
+ * steps outside 1..ABNN_PROP_MAX_STEPS and for In != Out.                      */
+abnn_status abnn_propagate_iterate_enqueue(abnn_brain* b, const abnn_propagate_config* cfg, uint32_t steps, int32_t* x_dev, uint64_t* work_dev, uint64_t* trace_dev, void* stream);
+/* The rule on the host, without a device or a handle, over interchange records
+ * of a brain of n_nrn neurons with the given base_scale; x holds n_nrn int32,
+ * out abnn_propagate_words(cfg, n_nrn) u64.                                    */
+abnn_status abnn_propagate_host(const abnn_propagate_config* cfg, uint64_t n_nrn, float base_scale, const abnn_synapse* syn, uint64_t n_syn, const int32_t* x, uint64_t* out);
+/* The rescale on the host: `out` is a result, x (n_nrn int32) is rewritten over
+ * Out, trace_row (8 u64) may be null.                                          */
+abnn_status abnn_propagate_rescale_host(const abnn_propagate_config* cfg, uint64_t n_nrn, const uint64_t* out, int32_t* x, uint64_t* trace_row);
+
 /* ---- spike recorder -----------------------------------------
  * A recorder attached to a handle.  While it is on, every pass the handle
  * completes (abnn_traverse, the passes inside abnn_engine_run, abnn_shard_commit

@@ -68,6 +68,12 @@ abnn_status abnn_debug_comm_allgather(abnn_comm* c, void* buf, uint64_t bytes, u
  * is not counted.  Not synchronous, touches no device. */
 uint64_t abnn_debug_live_allocations(void);
 
+/* The forward instance of the handle's following propagations (abnn_propagate_*):
+ * 0 = chosen on the device from the non-zero count of x (the default), 1 = the
+ * sparse one, 2 = the dense one.  The result's words do not depend on it.
+ * Not synchronous. */
+abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

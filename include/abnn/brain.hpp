@@ -168,6 +168,38 @@ struct HopsView {
     }
 };
 
+// A view of a propagation result (abnn.h abnn_propagate: the header and y); it
+// does not own the words.
+struct PropagateView {
+    const uint64_t* words = nullptr;
+    uint64_t count = 0;  // the neurons of the out-range
+    PropagateView(const uint64_t* w, const abnn_propagate_config& cfg, uint64_t n_nrn)
+        : words(w), count(cfg.out_count ? cfg.out_count : n_nrn) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }
+    uint64_t followed() const { return words[2]; }
+    uint64_t skipped() const { return words[3]; }  // followed records whose coefficient is not summable
+    uint64_t nonzero() const { return words[4]; }  // non-zero x in the in-range
+    uint64_t sum_abs_x() const { return words[5]; }
+    // y()[j], j < count: the sum for neuron out_first + j, 8 fractional bits more than x
+    const int64_t* y() const { return reinterpret_cast<const int64_t*>(words + ABNN_PROP_HEADER_WORDS); }
+};
+
+// The outcome of Brain::branching: the trace (steps rows of ABNN_PROP_TRACE_WORDS
+// u64, abnn.h) and the last rescaled plane.
+struct Branching {
+    std::vector<uint64_t> trace;
+    std::vector<int32_t> x;
+    size_t steps() const { return trace.size() / ABNN_PROP_TRACE_WORDS; }
+    // step k's eigenvalue estimate (sum |y| / 256) / sum |x|, 0 when x was zero
+    double estimate(size_t k) const
+    {
+        const uint64_t* r = trace.data() + k * ABNN_PROP_TRACE_WORDS;
+        return r[1] ? (static_cast<double>(r[2]) / 256.0) / static_cast<double>(r[1]) : 0.0;
+    }
+    double ratio() const { return steps() ? estimate(steps() - 1) : 0.0; }
+};
+
 // A view of a correlogram (abnn.h abnn_corr: the header and the plane); it does
 // not own the words.
 struct CorrView {
@@ -697,6 +729,55 @@ public:
     void hops_step_enqueue(const abnn_hops_config& cfg, uint32_t step, uint64_t* out_dev, void* stream = nullptr) const
     {
         check(abnn_hops_step_enqueue(h_, &cfg, step, out_dev, stream), "abnn_hops_step_enqueue");
+    }
+    // Signal propagation on the device (abnn_propagate; the rule is in abnn.h):
+    // x holds n_neuron() int32; the result's words, to be read through a PropagateView.
+    std::vector<uint64_t> propagate(const abnn_propagate_config& cfg, const std::vector<int32_t>& x) const
+    {
+        if (x.size() != n_neuron()) throw std::runtime_error("Brain::propagate: x must hold n_neuron() entries");
+        const uint64_t words = abnn_propagate_words(&cfg, n_neuron());
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_propagate(h_, &cfg, x.data(), w.data(), words), "abnn_propagate");
+        return w;
+    }
+    // Enqueue only: x_dev is device memory of n_neuron() int32 (16-byte aligned), out_dev of
+    // abnn_propagate_words(&cfg, n_neuron()) u64.
+    void propagate_enqueue(const abnn_propagate_config& cfg, const int32_t* x_dev, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_propagate_enqueue(h_, &cfg, x_dev, out_dev, stream), "abnn_propagate_enqueue");
+    }
+    // Enqueue only: the rescale of out_dev into x_dev and its trace row (8 u64 of device memory, or null).
+    void propagate_rescale_enqueue(const abnn_propagate_config& cfg, const uint64_t* out_dev, int32_t* x_dev,
+                                   uint64_t* trace_row_dev = nullptr, void* stream = nullptr) const
+    {
+        check(abnn_propagate_rescale_enqueue(h_, &cfg, out_dev, x_dev, trace_row_dev, stream),
+              "abnn_propagate_rescale_enqueue");
+    }
+    // Enqueue only: `steps` times propagate and rescale with nothing returning to the host; trace_dev holds
+    // steps x ABNN_PROP_TRACE_WORDS u64.
+    void propagate_iterate_enqueue(const abnn_propagate_config& cfg, uint32_t steps, int32_t* x_dev, uint64_t* work_dev,
+                                   uint64_t* trace_dev, void* stream = nullptr) const
+    {
+        check(abnn_propagate_iterate_enqueue(h_, &cfg, steps, x_dev, work_dev, trace_dev, stream),
+              "abnn_propagate_iterate_enqueue");
+    }
+    // The branching ratio: `steps` power iterations of cfg (its in-range and out-range the same) from x.
+    // This convenience owns no device memory: every step is the synchronous propagation and the host's
+    // rescale (abnn_propagate_rescale_host: the same words as the device's); a caller with device planes
+    // enqueues propagate_iterate_enqueue instead.
+    Branching branching(const abnn_propagate_config& cfg, uint32_t steps, std::vector<int32_t> x) const
+    {
+        if (steps < 1 || steps > ABNN_PROP_MAX_STEPS || cfg.in_first != cfg.out_first || cfg.in_count != cfg.out_count)
+            throw std::runtime_error("Brain::branching: steps in 1..ABNN_PROP_MAX_STEPS, in-range == out-range");
+        Branching b;
+        b.trace.assign(static_cast<size_t>(steps) * ABNN_PROP_TRACE_WORDS, 0);
+        for (uint32_t k = 0; k < steps; ++k) {
+            const std::vector<uint64_t> w = propagate(cfg, x);
+            check(abnn_propagate_rescale_host(&cfg, n_neuron(), w.data(), x.data(), b.trace.data() + k * ABNN_PROP_TRACE_WORDS),
+                  "abnn_propagate_rescale_host");
+        }
+        b.x = std::move(x);
+        return b;
     }
     // The spike recorder (abnn_spikes_*; the contract is in abnn.h): from
     // record_spikes on, every pass appends its spike list to device buffers.

@@ -561,6 +561,11 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_raw_wave_clock", C.c_int, [_VP, C.c_uint64, _U32, _U32, C.POINTER(C.c_uint64), C.c_uint64, _VP]),
     ("abnn_debug_live_allocations", C.c_uint64, []),
     ("abnn_debug_set_propagate_path", C.c_int, [_VP, C.c_int]),
+    ("abnn_debug_index_state", C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
+    ("abnn_debug_index_mask_dirty", C.c_int, [_VP, C.POINTER(C.c_uint64)]),
+    ("abnn_debug_set_indexed", C.c_int, [_VP, C.c_int]),
+    ("abnn_debug_set_fused", C.c_int, [_VP, C.c_int]),
+    ("abnn_debug_index_copy", C.c_int, [_VP, _PU32, C.c_uint64, _PU32, C.c_uint64]),
 ]
 
 

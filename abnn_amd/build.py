@@ -37,13 +37,13 @@ HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip")
                os.path.join(CSRC, "degree.hip"), os.path.join(CSRC, "select.hip"),
                os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
                os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip"), os.path.join(CSRC, "reorder.hip"),
-               os.path.join(CSRC, "propagate.hip")]
+               os.path.join(CSRC, "propagate.hip"), os.path.join(CSRC, "index.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
                           os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "pool.h"),
-                          os.path.join(CSRC, "propagate.h"), os.path.join(CSRC, "runs.h"),
+                          os.path.join(CSRC, "propagate.h"), os.path.join(CSRC, "runs.h"), os.path.join(CSRC, "index.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")

@@ -29,7 +29,9 @@
 #include "corr.h"
 #include "reorder.h"
 #include "propagate.h"
+#include "index.h"
 #include "pool.h"
+#include "../../include/abnn/abnn_debug.h"
 
 using namespace abnn;
 
@@ -65,6 +67,26 @@ uint64_t visited_events(const abnn_dims& d, uint32_t mode)
 
 struct EventPair {
     hipEvent_t a, b;
+};
+
+// The indexed fused pass (index.h): the src index of records
+// [0, E), the per-pass event mask, and the bookkeeping of when they hold.
+struct IndexState {
+    uint32_t *row = nullptr, *off = nullptr, *mask = nullptr, *info = nullptr;
+    uint4* heavy = nullptr;        // the lists above index.hip's kHeavyLen entries, in chunks (launch_index_heavy)
+    uint32_t heavy_chunks = 0;
+    uint64_t mask_words = 0;
+    bool built = false;            // row / off describe the records as they are (index_invalidate clears it)
+    uint64_t entries = 0;          // records of [0, E) with a live src
+    uint32_t max_degree = 0;       // the longest list
+    float build_ms = 0.0f;         // the last build, a HIP event pair around its launches
+    uint64_t eligible = 0;         // consecutive eligible passes since the records last changed
+    bool last_indexed = false;     // the last pass ran the mask flavour
+    uint64_t indexed_passes = 0;
+    int flavour = -1;              // the last fused pass's (0 stream, 1 mask): the partition's cost history is per flavour
+    int mode = 1;                  // ABNN_INDEXED: 0 never, 1 the rule (index_pass_rule), 2 whenever the index is valid
+    uint32_t after = 4;            // ABNN_INDEX_AFTER: eligible passes before the build
+    uint64_t max_mb = 4096;        // ABNN_INDEX_MAX_MB: no index above it
 };
 
 }  // namespace
@@ -167,6 +189,7 @@ struct abnn_brain {
     // reloaded (abnn_load_bnn / abnn_load_flat / abnn_generate_synapses / an
     // upload of every record)
     bool records_invalid = false;
+    IndexState ix;  // the indexed fused pass: src index, event mask, policy (index_* below)
 
     // On the handle's device.  The device memory goes with the pool; the rest
     // is the timing events and the error word.
@@ -310,8 +333,11 @@ abnn_status validate_records(const abnn_brain* b, const abnn_synapse* s, uint64_
 // Host-written records may hold tombstones (a saved pruned brain): recount the
 // structural update's per-block tally over them (structural updates on only:
 // d.dead exists when compact_every > 0).
+void index_invalidate(abnn_brain* b);
+
 abnn_status retally(abnn_brain* b, uint64_t first, uint64_t n)
 {
+    index_invalidate(b);  // the records were written: their src may have changed
     if (!b->d.dead || n == 0) return ABNN_OK;
     HIP_TRY(launch_tally_dead(b->d.syn, b->dims.n_syn, b->d.dead, first, n, nullptr));
     HIP_TRY(hipDeviceSynchronize());
@@ -375,6 +401,28 @@ uint64_t stream_pin_bytes()
     return mib << 20;
 }
 
+// The src index (index.h) holds only while the src of records [0, E) and E
+// itself are what it was built from.  Every writer of a record's src, of a
+// tombstone or of the record count calls this: upload, generate, the graph
+// builder and the file loads (through retally), the edit's KILL, the reorder,
+// a snapshot roll-back, the structural update, and configure when E changes.
+// The buffers are freed; the index is built again after ABNN_INDEX_AFTER
+// eligible passes.  (hipFree waits for the device: no pass still reads them.)
+void index_invalidate(abnn_brain* b)
+{
+    IndexState& x = b->ix;
+    if (x.row || x.off || x.mask || x.info || x.heavy) {
+        (void)hipSetDevice(b->device);
+        b->pool.release(&x.row, &x.off, &x.mask, &x.info, &x.heavy);
+    }
+    x.heavy_chunks = 0;
+    x.built = false;
+    x.entries = 0;
+    x.max_degree = 0;
+    x.mask_words = 0;
+    x.eligible = 0;
+}
+
 // Sweep partition for the current record count: visited events, wave
 // iterations and the persistent gate grid (one range per wave).  Run at
 // creation and after every structural update.
@@ -382,7 +430,9 @@ void configure(abnn_brain* b)
 {
     DeviceState& d = b->d;
     d.n_syn = b->dims.n_syn;
-    d.events = visited_events(b->dims, b->params.mode);
+    const uint64_t ev = visited_events(b->dims, b->params.mode);
+    if (ev != d.events) index_invalidate(b);
+    d.events = ev;
     const uint64_t iters = (d.events + d.iter_events - 1) / d.iter_events;
     d.iters = (uint32_t)iters;
     uint64_t G = std::min<uint64_t>(iters, std::min<uint64_t>((uint64_t)b->cus * b->per_cu, kMaxGateBlocks));
@@ -544,6 +594,9 @@ abnn_status structural_update(abnn_brain* b)
     }
     b->dims.n_syn = n - w[2] + w[4];
     b->structural_updates += 1;
+    // (an update that found no tombstone and appended nothing moved no record: the index holds;
+    // when E changes, configure drops it as well)
+    if (w[2] != 0 || w[4] != 0) index_invalidate(b);
     return repartition(b);
 }
 
@@ -572,7 +625,7 @@ bool build_next_ok(const abnn_brain* b)
 
 // This pass's recent-spike buffers (triple-buffered by pass % 3) and, unless
 // the previous pass built them, the bitmap from lastFired (k_bitmap).
-abnn_status pass_buffers(abnn_brain* b, hipStream_t s)
+abnn_status pass_buffers(abnn_brain* b, hipStream_t s, bool* was_prebuilt = nullptr)
 {
     DeviceState& d = b->d;
     const uint64_t p = b->rot;  // not pass_host: set_scalars may move that
@@ -587,6 +640,7 @@ abnn_status pass_buffers(abnn_brain* b, hipStream_t s)
     const bool prebuilt = b->next_built && b->built_stim[0] == b->stim_first &&
                           b->built_stim[1] == b->stim_count;
     b->next_built = false;
+    if (was_prebuilt) *was_prebuilt = prebuilt;
     if (!prebuilt) HIP_TRY(launch_bitmap(d, b->kp, b->stim_first, b->stim_count, s));
     b->stim_ring[b->pass_host % kFiredRing][0] = b->stim_first;
     b->stim_ring[b->pass_host % kFiredRing][1] = b->stim_count;
@@ -613,6 +667,92 @@ void plan_build(abnn_brain* b)
     }
 }
 
+// Handles that may run indexed passes: sweep mode, single GPU, none of
+// track_visits, pruning, synaptogenesis; the lean fused instance; record
+// arrays never handed out; E below 2^32 (off[] holds u32 offsets) and the
+// index within ABNN_INDEX_MAX_MB.
+uint64_t index_bytes(const abnn_brain* b)
+{
+    return 4 * b->d.events + 4 * (b->n_nrn + 1) + 4 * index_mask_words(b->d.iters, b->d.iter_events);
+}
+
+bool index_eligible(const abnn_brain* b)
+{
+    const DeviceState& d = b->d;
+    const abnn_params& p = b->params;
+    const bool plastic = p.w_prune > 0.0f || (d.grown != nullptr && p.p_new > 0.0f);
+    return b->ix.mode != 0 && p.mode == ABNN_MODE_SWEEP && !p.track_visits && !plastic && d.lean && !d.g2src &&
+           !b->ext_ptrs && b->dims.global_events == 0 && d.events > 0 && d.events < (1ull << 32) &&
+           index_bytes(b) <= (b->ix.max_mb << 20);
+}
+
+// The default rule (ABNN_INDEXED=1).  When this pass's bitmap was built from
+// the spike lists (build_next_ok held when the previous pass built it), the
+// recent set holds at most window_pre x (max_spikes + stimulus count) neurons
+// (the largest stimulus of the window's passes): the pass is indexed iff that
+// bound times the index's largest degree is at most E / 8.  A bitmap from
+// k_bitmap (the first passes, where lastFired = 0 makes every neuron recent;
+// host writes) has no such bound: the pass streams.
+bool index_pass_rule(const abnn_brain* b, bool prebuilt)
+{
+    if (!prebuilt) return false;
+    const uint64_t W = b->params.window_pre, p = b->pass_host;
+    uint64_t stim = b->stim_count;
+    for (uint64_t q = p >= W ? p - W : 0; q <= p; ++q) stim = std::max(stim, b->stim_ring[q % kFiredRing][1]);
+    const uint64_t bound = W * ((uint64_t)b->params.max_spikes + stim);
+    return bound * b->ix.max_degree <= b->d.events / 8;
+}
+
+// Builds the index on the pass's stream, with one read-back (the largest
+// degree and the entry count) and a HIP event pair around its launches.  No
+// memory for it: the handle goes on streaming (ABNN_INDEXED=0 from here on).
+abnn_status index_build(abnn_brain* b, hipStream_t s)
+{
+    IndexState& x = b->ix;
+    const DeviceState& d = b->d;
+    index_invalidate(b);
+    DeviceTemp<uint32_t> cursor, part;
+    x.mask_words = index_mask_words(d.iters, d.iter_events);
+    abnn_status st = b->pool.alloc_all({raw(&x.row, b->n_nrn + 1), raw(&x.off, d.events), zeroed(&x.mask, x.mask_words),
+                                        zeroed(&x.info, 4)});
+    if (st == ABNN_OK) st = cursor.alloc(b->n_nrn + 1, false);
+    if (st == ABNN_OK) st = part.alloc(index_tiles(b->n_nrn) + 1, false);
+    if (st != ABNN_OK) {
+        index_invalidate(b);
+        x.mode = 0;
+        return st == ABNN_ERR_OOM ? ABNN_OK : st;
+    }
+    hipEvent_t ea = nullptr, eb = nullptr;
+    HIP_TRY(hipEventCreate(&ea));
+    hipError_t e = hipEventCreate(&eb);
+    uint32_t info[4] = {0, 0, 0, 0};
+    float ms = 0.0f;
+    if (e == hipSuccess) e = hipEventRecord(ea, s);
+    if (e == hipSuccess) e = launch_index_build(d.syn, d.events, b->n_nrn, x.row, cursor.dev, part.dev, x.off, x.info, (uint32_t)b->cus, s);
+    if (e == hipSuccess) e = hipEventRecord(eb, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(info, x.info, sizeof(info), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, ea, eb);
+    (void)hipEventDestroy(ea);
+    if (eb) (void)hipEventDestroy(eb);
+    HIP_TRY(e);
+    x.max_degree = info[0];
+    x.entries = info[1];
+    x.build_ms = ms;
+    if (info[2]) {  // the heavy list (the build's time leaves this one small launch out)
+        st = b->pool.alloc(raw(&x.heavy, info[2]));
+        if (st != ABNN_OK) {
+            index_invalidate(b);
+            x.mode = 0;
+            return st == ABNN_ERR_OOM ? ABNN_OK : st;
+        }
+        HIP_TRY(launch_index_heavy(x.row, b->n_nrn, x.heavy, info[2], x.info, s));
+    }
+    x.heavy_chunks = info[2];
+    x.built = true;
+    return ABNN_OK;
+}
+
 // A sharded pass takes the fused path (two launches around the exchange:
 // k_gate in shard mode, k_shard_walk) where a single-GPU pass would.
 bool shard_fused(const abnn_brain* b)
@@ -629,6 +769,9 @@ abnn_status run_gate(abnn_brain* b, int32_t* xchg_out, hipStream_t s)
     if (xchg_out && shard_fused(b)) return run_shard_fused_gate(b, xchg_out, s);
     ST_TRY(pass_buffers(b, s));
     b->last_pass_fused = false;
+    b->ix.eligible = 0;  // not an eligible pass (index_eligible): the count is of consecutive ones
+    b->ix.last_indexed = false;
+    b->ix.flavour = 0;
     EventPair* ev = nullptr;
     ST_TRY(time_begin(b, s, &ev));
     HIP_TRY(launch_gate(b->d, b->kp, s));
@@ -675,18 +818,41 @@ abnn_status run_apply(abnn_brain* b, const int32_t* gathered, uint32_t world, ui
 // kFused>): gate, look-back budget walk, weight update, stamps, pass end.  Its
 // prologue computes the next pass's partition (range_bounds_next) from the
 // previous fused pass's gate costs.
+//
+// The pass is indexed (DESIGN.md §5 "Indexed pass": k_index_mark, then the
+// mask flavour of the same launch) iff the handle is eligible, the index is
+// valid and the rule admits it; otherwise it streams.  Results never depend on
+// the choice.  The host decides from what it knows without reading the device.
 abnn_status run_fused(abnn_brain* b, hipStream_t s)
 {
     DeviceState& d = b->d;
-    ST_TRY(pass_buffers(b, s));
+    IndexState& x = b->ix;
+    const bool eligible = index_eligible(b);
+    if (eligible && !x.built && x.eligible >= x.after) ST_TRY(index_build(b, s));
+    bool prebuilt = false;
+    ST_TRY(pass_buffers(b, s, &prebuilt));
     plan_build(b);
-    d.prologue_adapt = b->last_pass_fused && d.adapt_ranges ? 1u : 0u;
+    const bool indexed = eligible && x.built && (x.mode == 2 || index_pass_rule(b, prebuilt));
+    // the partition adapts on the costs of its own flavour: after a change of
+    // flavour the bounds stay for one pass (fused_next_bounds copies them)
+    d.prologue_adapt = b->last_pass_fused && x.flavour == (indexed ? 1 : 0) && d.adapt_ranges ? 1u : 0u;
     d.cost_in = b->cost_buf[b->cost_parity ^ 1u];
     d.cost_out = b->cost_buf[b->cost_parity];
+    d.indexed = indexed ? 1u : 0u;
+    d.ev_mask = x.mask;
     EventPair* ev = nullptr;
     ST_TRY(time_begin(b, s, &ev));
-    HIP_TRY(launch_fused_pass(d, b->kp, s));
+    hipError_t e = hipSuccess;
+    if (indexed)
+        e = launch_index_mark(d.bitmap, d.n_bitmap_words, d.n_nrn, x.row, x.off, x.mask, d.events, x.heavy, x.heavy_chunks, s);
+    if (e == hipSuccess) e = launch_fused_pass(d, b->kp, s);
+    d.indexed = 0u;
+    HIP_TRY(e);
     if (ev) HIP_TRY(hipEventRecord(ev->b, s));
+    x.flavour = indexed ? 1 : 0;
+    x.last_indexed = indexed;
+    x.indexed_passes += indexed ? 1u : 0u;
+    x.eligible = eligible ? x.eligible + 1 : 0;
     b->next_built = d.build_next != 0;
     b->built_stim[0] = b->stim_first;
     b->built_stim[1] = b->stim_count;
@@ -710,6 +876,9 @@ abnn_status run_shard_fused_gate(abnn_brain* b, int32_t* xchg, hipStream_t s)
     d.cost_out = b->cost_buf[b->cost_parity];
     d.shard_mode = 1;
     d.xchg = xchg;
+    b->ix.eligible = 0;  // a sharded pass streams; its costs are the stream flavour's
+    b->ix.last_indexed = false;
+    b->ix.flavour = 0;
     EventPair* ev = nullptr;
     ST_TRY(time_begin(b, s, &ev));
     const hipError_t e = launch_fused_pass(d, b->kp, s);
@@ -985,6 +1154,10 @@ abnn_status abnn_brain_create(const abnn_dims* dims, const abnn_params* params, 
     if (const char* env = std::getenv("ABNN_LEAN")) d.lean = std::atoi(env) != 0;
     if (const char* env = std::getenv("ABNN_SPEC")) d.spec_mode = (uint32_t)std::min(2, std::max(0, std::atoi(env)));
     b->force_full_bitmap = std::getenv("ABNN_FULL_BITMAP") != nullptr;
+    // the indexed pass: 0 never, 1 the rule (default), 2 whenever the index is valid
+    if (const char* env = std::getenv("ABNN_INDEXED")) b->ix.mode = std::min(2, std::max(0, std::atoi(env)));
+    if (const char* env = std::getenv("ABNN_INDEX_AFTER")) b->ix.after = (uint32_t)std::max(0, std::atoi(env));
+    if (const char* env = std::getenv("ABNN_INDEX_MAX_MB")) b->ix.max_mb = (uint64_t)std::max(0, std::atoi(env));
     d.adapt_ranges = std::getenv("ABNN_STATIC_RANGES") ? 0u : 1u;
     b->select_blocks = 4u * (uint32_t)std::max(1, b->cus);  // 32 waves per CU, as the census
     if (const char* env = std::getenv("ABNN_SELECT_BLOCKS")) b->select_blocks = (uint32_t)std::max(1, std::atoi(env));
@@ -1035,6 +1208,7 @@ abnn_status abnn_state_ptrs(abnn_brain* b, abnn_state* out)
     // the caller may write lastFired or the clock behind the handle's back:
     // rebuild the recent-spike bitmap from lastFired every pass from now on
     b->ext_ptrs = true;
+    index_invalidate(b);  // never used again (index_eligible): its memory goes now
     out->synapses = b->d.syn.lo;  // opaque (abnn_synapse_layout describes the arrays)
     out->last_fired = b->d.last_fired;
     out->last_visited = b->d.last_visited;
@@ -1053,6 +1227,7 @@ abnn_status abnn_synapse_layout(abnn_brain* b, abnn_layout* out)
     REQUIRE(b && out, "null argument");
     std::memset(out, 0, sizeof(*out));
     b->ext_ptrs = true;  // as abnn_state_ptrs: the caller may write behind the handle's back
+    index_invalidate(b);  // never used again (index_eligible): its memory goes now
     const uint64_t n = b->dims.syn_capacity + kDummyRecords;
     auto put = [&](void* p, uint64_t bytes, uint32_t eb, const char* name) {
         abnn_array_desc& a = out->arrays[out->n_arrays++];
@@ -1349,6 +1524,7 @@ abnn_status abnn_edit_enqueue(abnn_brain* b, const abnn_edit_config* cfg, const 
     ST_TRY(edit_check(cfg, b->n_nrn, plane_dev != nullptr));
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     HIP_TRY(hipSetDevice(b->device));
+    if (cfg->op == ABNN_EDIT_KILL) index_invalidate(b);  // tombstones: their src leaves the index
     // the host knows n_syn: structural updates synchronise
     HIP_TRY(launch_edit(b->d.syn, b->dims.n_syn, edit_rule(*cfg, b->n_nrn, b->dims.syn_offset), plane_dev, b->d.dead,
                         out_dev, b->edit_blocks, b->edit_nt, pick(b, stream)));
@@ -1364,6 +1540,7 @@ abnn_status abnn_edit(abnn_brain* b, const abnn_edit_config* cfg, const float* p
             "abnn_edit: plane_count must equal the neurons of the SCALE op's range (N_NRN when it is not set), 0 otherwise");
     REQUIRE(!b->records_invalid, kRecordsInvalid);
     ST_TRY(sync_all(b));
+    if (cfg->op == ABNN_EDIT_KILL) index_invalidate(b);  // tombstones: their src leaves the index
     if (!b->edit_out) ST_TRY(b->pool.alloc(zeroed(&b->edit_out, ABNN_EDIT_HEADER_WORDS)));
     ST_TRY(b->pool.grow(&b->edit_plane, &b->edit_plane_cap, plane_count));
     if (plane_count)
@@ -1443,6 +1620,7 @@ abnn_status reorder_launch(abnn_brain* b, const abnn_reorder_config* cfg, const 
                            hipStream_t s)
 {
     const uint64_t n = b->dims.n_syn;  // the host knows n_syn: structural updates synchronise
+    index_invalidate(b);  // records move
     HIP_TRY(launch_reorder(b->d.syn, n, b->dims.syn_offset, *cfg, perm_dev, b->reorder, out_dev, b->reorder_blocks,
                            b->reorder_skip, s));
     HIP_TRY(launch_src32_sync(b->d.syn, n, s));
@@ -1655,6 +1833,7 @@ abnn_status abnn_snapshot_restore(abnn_brain* b, const abnn_snapshot* s, uint32_
         // [0, n) come back; what lies at and past n stays (as after a shrinking
         // structural update: a pass masks the events past its last one)
         const uint64_t n = s->n_syn;
+        index_invalidate(b);  // the records come back as they were captured
         if (n) {
             HIP_TRY(hipMemcpyAsync(d.syn.lo, s->syn.lo, n * 2, hipMemcpyDeviceToDevice, b->stream));
             HIP_TRY(hipMemcpyAsync(d.syn.hi, s->syn.hi, n, hipMemcpyDeviceToDevice, b->stream));
@@ -2841,6 +3020,65 @@ abnn_status abnn_debug_stream_pin(abnn_brain* b, uint32_t* pin_k)
 {
     REQUIRE(b && pin_k, "null argument");
     *pin_k = b->d.pin_k;
+    return ABNN_OK;
+}
+
+// The indexed pass (index.h).  out: {index built, its entries, its largest
+// degree, the last pass was indexed, indexed passes so far, consecutive
+// eligible passes, ABNN_INDEXED, E}; *build_ms: the last build.
+abnn_status abnn_debug_index_state(abnn_brain* b, uint64_t out[ABNN_DEBUG_INDEX_WORDS], double* build_ms)
+{
+    REQUIRE(b && out, "null argument");
+    const IndexState& x = b->ix;
+    out[0] = x.built ? 1 : 0;
+    out[1] = x.entries;
+    out[2] = x.max_degree;
+    out[3] = x.last_indexed ? 1 : 0;
+    out[4] = x.indexed_passes;
+    out[5] = x.eligible;
+    out[6] = (uint64_t)x.mode;
+    out[7] = b->d.events;
+    if (build_ms) *build_ms = x.build_ms;
+    return ABNN_OK;
+}
+
+// The event mask's non-zero words (0 between passes; 0 without an index).  Synchronous.
+abnn_status abnn_debug_index_mask_dirty(abnn_brain* b, uint64_t* words)
+{
+    REQUIRE(b && words, "null argument");
+    *words = 0;
+    ST_TRY(sync_all(b));
+    if (!b->ix.mask) return ABNN_OK;
+    HIP_TRY(launch_index_dirty(b->ix.mask, b->ix.mask_words, reinterpret_cast<unsigned long long*>(b->u64_scratch), b->stream));
+    return read_words(b, b->u64_scratch, words, 1);
+}
+
+// ABNN_INDEXED for this handle from now on (0 never, 1 the rule, 2 whenever the index is valid).
+abnn_status abnn_debug_set_indexed(abnn_brain* b, int mode)
+{
+    REQUIRE(b && mode >= 0 && mode <= 2, "abnn_debug_set_indexed: mode must be 0, 1 or 2");
+    b->ix.mode = mode;
+    return ABNN_OK;
+}
+
+// ABNN_FUSED for this handle's following single-GPU passes: 1 the fused launch where the shape has one, 0 gate + apply.
+abnn_status abnn_debug_set_fused(abnn_brain* b, int on)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(!b->pending_walk, "abnn_debug_set_fused: a sharded pass is half done (abnn_shard_apply)");
+    b->use_fused = on != 0;
+    return ABNN_OK;
+}
+
+// row[0, n_row) and off[0, n_off) of a built index (n_row <= N_NRN + 1, n_off <= entries).  Synchronous.
+abnn_status abnn_debug_index_copy(abnn_brain* b, uint32_t* row, uint64_t n_row, uint32_t* off, uint64_t n_off)
+{
+    REQUIRE(b && (row || n_row == 0) && (off || n_off == 0), "null argument");
+    ST_TRY(sync_all(b));
+    REQUIRE(b->ix.built, "abnn_debug_index_copy: no index is built");
+    REQUIRE(n_row <= b->n_nrn + 1 && n_off <= b->ix.entries, "abnn_debug_index_copy: range out of bounds");
+    if (n_row) HIP_TRY(hipMemcpy(row, b->ix.row, n_row * 4, hipMemcpyDeviceToHost));
+    if (n_off) HIP_TRY(hipMemcpy(off, b->ix.off, n_off * 4, hipMemcpyDeviceToHost));
     return ABNN_OK;
 }
 

@@ -22,6 +22,10 @@
 //                (brain.metal:125-126), workgroup 0 ends the pass (rBar
 //                brain.metal:110-113, clock brain.metal:129).  The next pass's
 //                bitmap and filter are built on the way (set-only atomics).
+//   k_gate<..., kFused, kLean, !kShard, kMask> : the same pass over the
+//                per-pass event mask that k_index_mark (index.hip) set from
+//                the exact bitmap, instead of over the src stream (the indexed
+//                pass; capi.hip run_fused chooses per pass).
 //   k_gate<..., !kFused> + k_apply : the two-kernel pass (sharded passes,
 //                random-edge mode, ABNN_FUSED=0): the gate writes per-chunk
 //                survivor slots, k_apply walks the budget over them, updates
@@ -48,6 +52,7 @@
 
 #include "engine.h"
 #include "device.h"
+#include "index.h"
 
 #pragma clang fp contract(off)
 
@@ -500,7 +505,11 @@ __device__ __forceinline__ uint4 range_totals(const DeviceState& d, uint32_t r) 
 // (the workgroup is predicted to lie below the pass's budget cut) the updated
 // weight is stored here already; the walk restores w where the prediction was
 // wrong.
-template <int R, bool kRandom, bool kFused, bool kTail, class At>
+// kMask (the indexed pass, index.h): the staged events ARE the pre-gated ones
+// (the event mask is exact), staged as {offset} alone: g1 holds for every
+// entry, neither the bitmap word nor the second-level filter is read, and src
+// is never needed (no synaptogenesis in an indexed pass: g2src is null).
+template <int R, bool kRandom, bool kFused, bool kTail, bool kMask = false, class At>
 __device__ __forceinline__ uint4 refrac_chunk(const DeviceState& d, const KernelParams& kp, uint64_t region,
                                               uint64_t base, uint32_t n, uint64_t now, uint64_t pass, float Rw,
                                               float rbw, bool spec, uint32_t crange, uint32_t c0,
@@ -524,7 +533,21 @@ __device__ __forceinline__ uint4 refrac_chunk(const DeviceState& d, const Kernel
         // it has no false negatives): the exact bitmap word of src and the
         // record's {dst, w}.  (Round 4 read the bitmap word for every staged
         // event: each random read costs the CU's vector-memory path)
-        if constexpr (!kTail) {
+        if constexpr (kMask) {
+            // one round trip: {dst, w} of every staged event (the tail's form:
+            // lanes past n read record 0 and discard it)
+            uint2 e[R];
+#pragma unroll
+            for (int j = 0; j < R; ++j) e[j] = at(kTail || b0 + j * 64 + lane < n ? b0 + j * 64 + lane : 0u);
+#pragma unroll
+            for (int j = 0; j < R; ++j) {
+                rel[j] = e[j].x;
+                src[j] = 0u;
+                bw[j] = 0u;
+                f2[j] = b0 + j * 64 + lane < n;
+                dw[j] = d.syn.dw[f2[j] ? record_of(rel[j]) : 0];
+            }
+        } else if constexpr (!kTail) {
 #pragma unroll
             for (int j = 0; j < R; ++j) {
                 const uint32_t q = b0 + j * 64 + lane;
@@ -566,7 +589,7 @@ __device__ __forceinline__ uint4 refrac_chunk(const DeviceState& d, const Kernel
         }
 #pragma unroll
         for (int j = 0; j < R; ++j) {
-            const bool g1 = f2[j] && src[j] < nn && ((bw[j] >> (src[j] & 31u)) & 1u);  // brain.metal:73-77, exact
+            const bool g1 = kMask ? f2[j] : f2[j] && src[j] < nn && ((bw[j] >> (src[j] & 31u)) & 1u);  // brain.metal:73-77, exact
             bw[j] = g1;
             if (!g1) dw[j] = make_uint2(0xFFFFFFFFu, 0u);
             dst[j] = dw[j].x;  // tombstones (dst = 0xFFFFFFFF) never pass
@@ -617,7 +640,7 @@ __device__ __forceinline__ uint4 refrac_chunk(const DeviceState& d, const Kernel
                     const uint32_t isi = __float_as_uint((float)age32(now, ld[j])) | (cand ? 0x80000000u : 0u);
                     d.g2x[o] = make_uint4(rel[j], isi, __float_as_uint(w[j]), dst[j]);
                 }
-                if (d.g2src) d.g2src[o] = src[j];  // synaptogenesis keeps src
+                if (!kMask && d.g2src) d.g2src[o] = src[j];  // synaptogenesis keeps src
                 if (tg == 0) {  // read by workgroup 0 at the pass's end (fused pass): write-through,
                                 // drained before this wave reaches the barrier its workgroup's
                                 // look-back word is published behind (the sc1 hand-off form,
@@ -1333,9 +1356,27 @@ __device__ __forceinline__ void set_priority(uint32_t p)
 // weight update of k_apply: apply_event), and the last workgroup ends the pass
 // (fused_finalize).  Its survivors are written contiguously from the range's
 // region start (no per-chunk slots: the wave walks them itself).
-template <int BLOCK, int K, int FW, bool kTrack, bool kRandom, bool kFused, bool kLean = false, bool kShard = false>
+//
+// kMask (the indexed pass, index.h; a lean fused instance only): the wave
+// streams its range's bits of the per-pass event mask -- one bit per event,
+// set by k_index_mark for exactly the events whose src is recent -- where the
+// other flavours stream the 3-B src codes: no filter image, no filter test.
+// Layout 4 gives a lane 8 consecutive events of a 512-event block, which is
+// one mask byte per lane, so the stage order (lane, k) and everything after
+// staging is the stream flavour's.  The mask is read kMaskRoundBytes per wave
+// and round (64 iterations at K = 8), every load of a round in flight at once
+// and the next round's issued before this one is scanned, and laid into the
+// wave's slice of the 64 KiB of LDS the filter image does not need.  A 1-KiB
+// piece is scanned from the lanes' own 16-B words (event order (lane, bit));
+// a piece with more hits than the stage has room for block by block from the
+// slice, in the (lane, k) order with the quarter path.  The wave stores zero
+// over the non-zero 16-B words of its own range, so the mask is clean again
+// when the pass ends.  It stages {offset} alone (refrac_chunk kMask).
+template <int BLOCK, int K, int FW, bool kTrack, bool kRandom, bool kFused, bool kLean = false, bool kShard = false,
+          bool kMask = false>
 __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
 {
+    static_assert(!kMask || (kFused && kLean && !kShard && !kTrack && !kRandom), "the mask flavour is a lean fused instance");
     constexpr int NW = BLOCK / 64;
     constexpr uint32_t IE = 64 * K;
     constexpr int KD = kTrack ? K : 1;                 // dst words in flight (track_visits)
@@ -1361,6 +1402,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     // prologue.  One wave-instruction copies 1 KiB (LDS: wave-uniform base +
     // 16 B per lane); the first use of an ordinary load's result waits for it.
     static_assert((FW / 2) % BLOCK == 0, "the filter copy is FW / 2 / BLOCK uint4 per thread");
+    if constexpr (!kMask) {
 #pragma unroll
     for (int c = 0; c < FW / 2 / BLOCK; ++c)
         __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(d.filter) + c * BLOCK + tid,
@@ -1371,6 +1413,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
         if (i0 + tid < kF2Words / 4)
             __builtin_amdgcn_global_load_lds(reinterpret_cast<const uint4*>(d.filter + 2 * FW) + i0 + tid,
                                              reinterpret_cast<uint4*>(s_f2) + i0 + (tid & ~63u), 16, 0, 0);
+    }
     // fused: the previous pass's range costs (the next partition's input,
     // fused_next_bounds) go to LDS the same way
     if constexpr (kFused) {
@@ -1491,9 +1534,31 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
             }
         }
     };
+    // kMask: the mask in flight -- BI bytes per iteration, RI iterations per
+    // round of kMaskRoundBytes, ML 16-B loads per lane and round (wave-
+    // instruction j reads bytes [1024 j, 1024 j + 1024) of the round); a
+    // round is read whole, so past the range's end it holds the next ranges'
+    // bytes (never scanned, never cleared here) and past the sweep's the
+    // mask's padding (index.h).  mrow: the wave's slice of the LDS the filter
+    // image does not need.
+    constexpr uint32_t BI = IE / 8, RI = kMaskRoundBytes / BI;
+    constexpr int ML = kMaskRoundBytes / 1024;
+    static_assert(!kMask || (size_t)FW * sizeof(uint2) >= (size_t)NW * kMaskRoundBytes, "the mask rounds fit the filter's LDS");
+    u32x4 mk[ML];
+    u32x4* const mrow = reinterpret_cast<u32x4*>(s_fb) + wid * (kMaskRoundBytes / 16);
+    auto mask_at = [&](uint32_t it0) { return reinterpret_cast<u32x4*>(d.ev_mask) + (uint64_t)it0 * (BI / 16); };
+    auto mask_issue = [&](uint32_t it0) __attribute__((always_inline)) {
+        const u32x4* p = mask_at(it0);
+#pragma unroll
+        for (int j = 0; j < ML; ++j) mk[j] = p[j * 64 + lane];
+    };
     __builtin_amdgcn_sched_barrier(0);  // the LDS-DMAs above stay older than the records (see the wait below)
+    if constexpr (kMask) {
+        mask_issue(it_begin);
+    } else {
 #pragma unroll
     for (int j = 0; j < kDepth; ++j) issue(bufs[j], it_begin + j, it_begin + j < it_end);
+    }
     if constexpr (!kFused) {
         // the bitmap and images of the pass after next are zeroed here (the
         // next pass builds them: k_apply or k_bitmap), a slice per workgroup;
@@ -1512,7 +1577,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
         // would wait for vmcnt(0): the records' whole round trip, and until
         // round 4 the prologue's zeroing stores too, before the stream began.)
         // (kTrack: the {dst, w} pairs of the same events too, one iteration deep)
-        constexpr int kRecLoads = kDepth * (kRandom ? K * (kTrack ? 2 : 1) : NB8 * (2 + (kTrack ? 4 : 0)));
+        constexpr int kRecLoads = kMask ? ML : kDepth * (kRandom ? K * (kTrack ? 2 : 1) : NB8 * (2 + (kTrack ? 4 : 0)));
         __builtin_amdgcn_sched_barrier(0);
         wait_vm_lgkm0<kRecLoads>();
         __builtin_amdgcn_s_barrier();
@@ -1531,7 +1596,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     const uint32_t nn = (uint32_t)d.n_nrn;  // N_NRN < 2^32 (checked at create)
     uint32_t pend = 0, nch = 0;
     uint4 tot = make_uint4(0u, 0u, 0u, 0u);
-    auto stage_at = [&](uint32_t q) { return make_uint2(st_off[q], st_src[q]); };
+    auto stage_at = [&](uint32_t q) { return make_uint2(st_off[q], kMask ? 0u : st_src[q]); };  // kMask stages {offset}
     // wave-uniform: a full chunk through the refractory stage now; the (< 128)
     // entries past it move to the front of the stage
     // survivors go to chunk c's slots (the walk of k_apply takes chunks as
@@ -1540,7 +1605,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     auto chunk_out = [&]() {
         const uint64_t tc = __builtin_amdgcn_s_memrealtime();
         const uint64_t at = kFused ? region + tot.y : region + (uint64_t)nch * kChunk;
-        const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, false>(d, kp, region, at, kChunk, now, pass, Rw, rbw,
+        const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, false, kMask>(d, kp, region, at, kChunk, now, pass, Rw, rbw,
                                                                    spec, r, tot.z, s_f2, stage_at);
         if (!kFused && lane == 0) d.chunk_cnt[chunk_slot(region, nch)] = c;
         tot.x += c.x;
@@ -1564,7 +1629,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     // are staged (survivors go right after the range's earlier ones)
     auto flush_all = [&]() {
         const uint64_t tc = __builtin_amdgcn_s_memrealtime();
-        const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, false>(d, kp, region, region + tot.y, pend, now, pass, Rw,
+        const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, false, kMask>(d, kp, region, region + tot.y, pend, now, pass, Rw,
                                                                    rbw, spec, r, tot.z, s_f2, stage_at);
         tot.x += c.x;
         tot.y += c.y;
@@ -1760,10 +1825,100 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
             }
         }
     };
+    if constexpr (kMask) {
+        (void)step;
+        const uint8_t* mbytes = reinterpret_cast<const uint8_t*>(mrow);
+        constexpr uint32_t PI = 1024 / BI;  // iterations per 1-KiB piece of a round (one 16-B load per lane)
+        for (uint32_t r0 = it_begin; r0 < it_end; r0 += RI) {  // wave-uniform
+            // this round's words; the next round's loads next (a load issued
+            // behind a store would wait for it); then zero over the non-zero
+            // 16-B words of this range (a word never straddles an iteration:
+            // BI is a multiple of 16)
+            u32x4 cur[ML];
+#pragma unroll
+            for (int j = 0; j < ML; ++j) cur[j] = mk[j];
+            if (r0 + RI < it_end) mask_issue(r0 + RI);
+            u32x4* const mp = mask_at(r0);
+#pragma unroll
+            for (int j = 0; j < ML; ++j) {
+                // lane L's word of piece j: events 128 L .. 128 L + 127 of the piece, all of one iteration
+                const bool in = r0 + (uint32_t)(j * 1024 + lane * 16) / BI < it_end;
+                if (!in) cur[j] = u32x4{0u, 0u, 0u, 0u};  // the next ranges' bits
+                if ((cur[j].x | cur[j].y | cur[j].z | cur[j].w) != 0u) mp[j * 64 + lane] = u32x4{0u, 0u, 0u, 0u};
+                mrow[j * 64 + lane] = cur[j];  // (the pieces are taken from the wave's LDS slice: one copy of the code below)
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+#pragma unroll 1
+            for (uint32_t j = 0; j < (uint32_t)ML; ++j) {
+                if (r0 + j * PI >= it_end) break;  // wave-uniform
+                // Within a piece event order is (lane, bit): a lane's hits go
+                // to consecutive slots from the exclusive prefix of the lanes'
+                // counts.  Steady state: ~25 hits per piece.
+                const u32x4 v = mrow[j * 64 + lane];
+                const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+                const uint32_t c = __builtin_popcount(w4[0]) + __builtin_popcount(w4[1]) + __builtin_popcount(w4[2]) +
+                                   __builtin_popcount(w4[3]);
+                const uint32_t inc = wave_incl_scan(c);
+                const uint32_t hits = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
+                if (hits == 0) continue;  // wave-uniform
+                const uint32_t rel0 = (uint32_t)((uint64_t)(r0 + j * PI) * IE - region);  // the piece's first event
+                if (pend + hits <= SE) {  // wave-uniform
+                    uint32_t q = pend + inc - c;
+#pragma unroll
+                    for (int w = 0; w < 4; ++w)
+                        for (uint32_t x = w4[w]; x != 0u; x &= x - 1u)
+                            st_off[q++] = rel0 + 128u * lane + 32u * w + (uint32_t)__builtin_ctz(x);
+                    pend += hits;
+                    if (pend >= d.flush_at) flush_all();
+                    continue;
+                }
+                // A piece with more hits than the stage has room for (dense:
+                // the warm-up passes, the input->output block): through the
+                // wave's LDS slice again, one 512-event block at a time in the
+                // stream flavour's (lane, k) order -- a lane's byte of a block
+                // -- with its quarter path and a flush between quarters.
+#pragma unroll 1
+                for (uint32_t b = 0; b < 1024 / 64; ++b) {  // wave-uniform
+                    // bit k of the lane's byte: event 8 L + k of block b
+                    const uint32_t byte = mbytes[1024u * j + 64u * b + lane];
+                    const uint64_t bb = __ballot(byte != 0u);
+                    if (bb == 0) continue;  // wave-uniform
+                    const uint32_t relb = rel0 + 512u * b + 8u * lane;  // this lane's first event of the block
+                    const uint32_t cb = __builtin_popcount(byte);
+                    uint32_t P = 0, tot = 0;  // exclusive prefix of the counts, their total
+#pragma unroll
+                    for (int x = 0; x < 4; ++x) {  // counts <= 8: four bit planes
+                        const uint64_t bi = __ballot((cb >> x) & 1u);
+                        P += mbcnt64(bi) << x;
+                        tot += (uint32_t)__popcll(bi) << x;
+                    }
+                    const bool split = pend + tot > SE;  // wave-uniform: 128-event quarters (16 lanes each)
+#pragma unroll 1
+                    for (uint32_t u = 0; u < (split ? 4u : 1u); ++u) {  // wave-uniform
+                        const uint32_t p0 = split ? (uint32_t)__builtin_amdgcn_readlane((int)P, (int)(16u * u)) : 0u;
+                        const uint32_t p1 = !split || u == 3 ? tot
+                                                             : (uint32_t)__builtin_amdgcn_readlane((int)P, (int)(16u * u + 16u));
+                        const bool mine = !split || (lane >> 4) == u;
+                        uint32_t q = pend + P - p0;
+                        for (uint32_t x = mine ? byte : 0u; x != 0u; x &= x - 1u) st_off[q++] = relb + (uint32_t)__builtin_ctz(x);
+                        pend += p1 - p0;
+                        if (pend >= d.flush_at) flush_all();  // at most 128 past the threshold
+                    }
+                }
+            }
+            // the next round overwrites the slice
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront", "local");
+        }
+    } else {
     for (uint32_t it = it_begin; it < it_end; it += kDepth) {  // wave-uniform
 #pragma unroll
         for (int j = 0; j < kDepth; ++j)
             if (j == 0 || it + j < it_end) step(bufs[j], it + j);
+    }
     }
     const uint64_t t_stream = __builtin_amdgcn_s_memrealtime();
     if (!kFused && lane == 0 && d.wave_clock_on) {  // diagnostics (tools/wave_clock.py; the fused pass stores them in fused_end)
@@ -1791,7 +1946,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
         const bool lds_ok = kShard ? false : (kLean || (!d.shard_mode && !d.g2src));
         if (lds_ok && pend <= 256u) tail_lds = reinterpret_cast<uint4*>(s_stage[wid]);
     }
-    const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, true>(d, kp, region, tb, pend, now, pass, Rw, rbw, spec,
+    const uint4 c = refrac_chunk<kChunk / 64, kRandom, kFused, true, kMask>(d, kp, region, tb, pend, now, pass, Rw, rbw, spec,
                                                                r, tot.z, s_f2, stage_at, tail_lds);
     const uint64_t gt = ((t_stream - t_start) >> 2) + (uint64_t)nch * d.chunk_penalty;
     const uint32_t cost = len ? (uint32_t)(gt < 1 ? 1 : (gt > 0xFFFFu ? 0xFFFFu : gt)) : 0u;
@@ -2838,6 +2993,8 @@ hipError_t launch_fused_shape(const DeviceState& d, const KernelParams& kp, hipS
     const bool plastic = kp.w_prune > 0.0f || (d.grown != nullptr && kp.p_new > 0.0f);
     const bool lean = d.lean && !plastic;
     if (kp.track_visits) hipLaunchKernelGGL((k_gate<BLOCK, K, FW, true, false, true>), g, b, 0, s, d, kp);
+    else if (lean && !d.shard_mode && d.indexed)
+        hipLaunchKernelGGL((k_gate<BLOCK, K, FW, false, false, true, true, false, true>), g, b, 0, s, d, kp);
     else if (lean && !d.shard_mode) hipLaunchKernelGGL((k_gate<BLOCK, K, FW, false, false, true, true>), g, b, 0, s, d, kp);
     else if (lean) hipLaunchKernelGGL((k_gate<BLOCK, K, FW, false, false, true, true, true>), g, b, 0, s, d, kp);
     else hipLaunchKernelGGL((k_gate<BLOCK, K, FW, false, false, true>), g, b, 0, s, d, kp);
@@ -2873,7 +3030,10 @@ int occupancy_fused_shape(bool track)
     const hipError_t f = hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, k_gate<BLOCK, K, FW, false, false, true, true>, BLOCK, 0);
     const hipError_t h = hipOccupancyMaxActiveBlocksPerMultiprocessor(
         &q, k_gate<BLOCK, K, FW, false, false, true, true, true>, BLOCK, 0);
-    return e == hipSuccess && f == hipSuccess && h == hipSuccess ? std::min(n, std::min(m, q)) : 0;
+    int x = 0;
+    const hipError_t i = hipOccupancyMaxActiveBlocksPerMultiprocessor(
+        &x, k_gate<BLOCK, K, FW, false, false, true, true, false, true>, BLOCK, 0);
+    return e == hipSuccess && f == hipSuccess && h == hipSuccess && i == hipSuccess ? std::min(std::min(n, x), std::min(m, q)) : 0;
 }
 
 // Compiled gate shapes: threads per workgroup x events per lane x filter words.

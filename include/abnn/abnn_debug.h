@@ -74,6 +74,27 @@ uint64_t abnn_debug_live_allocations(void);
  * Not synchronous. */
 abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path);
 
+/* The indexed fused pass: out = {index built (0/1), its entries,
+ * its largest degree, the last pass was indexed (0/1), indexed passes so far,
+ * consecutive eligible passes since the records last changed, ABNN_INDEXED in
+ * force, the sweep's visited events E}; *build_ms (may be null): the last
+ * build's time.  Not synchronous. */
+#define ABNN_DEBUG_INDEX_WORDS 8
+abnn_status abnn_debug_index_state(abnn_brain* b, uint64_t out[ABNN_DEBUG_INDEX_WORDS], double* build_ms);
+/* The non-zero 32-bit words of the event mask: 0 between passes (the pass
+ * clears what it reads), 0 without an index.  Synchronous. */
+abnn_status abnn_debug_index_mask_dirty(abnn_brain* b, uint64_t* words);
+/* ABNN_INDEXED for this handle's following passes: 0 never indexed, 1 the
+ * default rule, 2 whenever the index is valid.  Not synchronous. */
+abnn_status abnn_debug_set_indexed(abnn_brain* b, int mode);
+/* ABNN_FUSED for this handle's following single-GPU passes: 1 = the fused
+ * launch where the gate shape has one (the default), 0 = the two-kernel pass
+ * (k_gate + k_apply).  Results do not depend on it.  Not synchronous. */
+abnn_status abnn_debug_set_fused(abnn_brain* b, int on);
+/* The built index's row[0, n_row) (n_row <= N_NRN + 1) and off[0, n_off)
+ * (n_off <= entries) to the host.  Synchronous; an error without an index. */
+abnn_status abnn_debug_index_copy(abnn_brain* b, uint32_t* row, uint64_t n_row, uint32_t* off, uint64_t n_off);
+
 #ifdef __cplusplus
 } /* extern "C" */
 #endif

@@ -566,6 +566,8 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_set_indexed", C.c_int, [_VP, C.c_int]),
     ("abnn_debug_set_fused", C.c_int, [_VP, C.c_int]),
     ("abnn_debug_index_copy", C.c_int, [_VP, _PU32, C.c_uint64, _PU32, C.c_uint64]),
+    ("abnn_debug_index_mask_copy", C.c_int, [_VP, _PU32, C.c_uint64, _PU32, C.c_uint64]),
+    ("abnn_debug_index_delta", C.c_int, [_VP, C.POINTER(C.c_uint64)]),
 ]
 
 

@@ -74,6 +74,11 @@ struct EventPair {
 struct IndexState {
     uint32_t *row = nullptr, *off = nullptr, *mask = nullptr, *info = nullptr;
     uint4* heavy = nullptr;        // the lists above index.hip's kHeavyLen entries, in chunks (launch_index_heavy)
+    // the marked set the mask stands for (index.h), N_NRN bits, and the buffer the next mark launch writes it to
+    // (run_fused swaps them); delta: two blocks of launch_index_mark's counters (4 * kDeltaSlots words each),
+    // delta_at the last launch's
+    uint32_t *marked = nullptr, *marked_next = nullptr, *delta = nullptr;
+    uint32_t delta_at = 0;
     uint32_t heavy_chunks = 0;
     uint64_t mask_words = 0;
     bool built = false;            // row / off describe the records as they are (index_invalidate clears it)
@@ -411,10 +416,11 @@ uint64_t stream_pin_bytes()
 void index_invalidate(abnn_brain* b)
 {
     IndexState& x = b->ix;
-    if (x.row || x.off || x.mask || x.info || x.heavy) {
+    if (x.row || x.off || x.mask || x.info || x.heavy || x.marked || x.marked_next || x.delta) {
         (void)hipSetDevice(b->device);
-        b->pool.release(&x.row, &x.off, &x.mask, &x.info, &x.heavy);
+        b->pool.release(&x.row, &x.off, &x.mask, &x.info, &x.heavy, &x.marked, &x.marked_next, &x.delta);
     }
+    x.delta_at = 0;
     x.heavy_chunks = 0;
     x.built = false;
     x.entries = 0;
@@ -673,7 +679,10 @@ void plan_build(abnn_brain* b)
 // index within ABNN_INDEX_MAX_MB.
 uint64_t index_bytes(const abnn_brain* b)
 {
-    return 4 * b->d.events + 4 * (b->n_nrn + 1) + 4 * index_mask_words(b->d.iters, b->d.iter_events);
+    // off, row, the mask, the marked set's two buffers, the mark's two counter blocks and info.  The heavy list is
+    // not in it: its length is known only after the build (16 B per 1024 entries of a list above kHeavyLen).
+    return 4 * b->d.events + 4 * (b->n_nrn + 1) + 4 * index_mask_words(b->d.iters, b->d.iter_events) +
+           2 * 4 * (uint64_t)b->d.n_bitmap_words + 2 * 4 * 4 * (uint64_t)kDeltaSlots + 4 * 4;
 }
 
 bool index_eligible(const abnn_brain* b)
@@ -714,7 +723,8 @@ abnn_status index_build(abnn_brain* b, hipStream_t s)
     DeviceTemp<uint32_t> cursor, part;
     x.mask_words = index_mask_words(d.iters, d.iter_events);
     abnn_status st = b->pool.alloc_all({raw(&x.row, b->n_nrn + 1), raw(&x.off, d.events), zeroed(&x.mask, x.mask_words),
-                                        zeroed(&x.info, 4)});
+                                        zeroed(&x.info, 4), zeroed(&x.marked, d.n_bitmap_words),
+                                        zeroed(&x.marked_next, d.n_bitmap_words), zeroed(&x.delta, 2 * 4 * kDeltaSlots)});
     if (st == ABNN_OK) st = cursor.alloc(b->n_nrn + 1, false);
     if (st == ABNN_OK) st = part.alloc(index_tiles(b->n_nrn) + 1, false);
     if (st != ABNN_OK) {
@@ -843,8 +853,17 @@ abnn_status run_fused(abnn_brain* b, hipStream_t s)
     EventPair* ev = nullptr;
     ST_TRY(time_begin(b, s, &ev));
     hipError_t e = hipSuccess;
-    if (indexed)
-        e = launch_index_mark(d.bitmap, d.n_bitmap_words, d.n_nrn, x.row, x.off, x.mask, d.events, x.heavy, x.heavy_chunks, s);
+    if (indexed) {
+        // the delta mark: the mask moves from the marked set to this pass's bitmap, which is the marked set from here on
+        // (a launch that failed moved nothing: the buffers and the counter blocks stay as they are)
+        const uint32_t at = x.delta_at ^ 4u * kDeltaSlots;
+        e = launch_index_mark(d.bitmap, x.marked, x.marked_next, d.n_bitmap_words, d.n_nrn, x.row, x.off, x.mask, d.events,
+                              x.heavy, x.heavy_chunks, x.delta + at, x.delta + x.delta_at, s);
+        if (e == hipSuccess) {
+            std::swap(x.marked, x.marked_next);
+            x.delta_at = at;
+        }
+    }
     if (e == hipSuccess) e = launch_fused_pass(d, b->kp, s);
     d.indexed = 0u;
     HIP_TRY(e);
@@ -3042,15 +3061,57 @@ abnn_status abnn_debug_index_state(abnn_brain* b, uint64_t out[ABNN_DEBUG_INDEX_
     return ABNN_OK;
 }
 
-// The event mask's non-zero words (0 between passes; 0 without an index).  Synchronous.
+// The event mask's words that differ from what the next indexed pass expects
+// (index.h's invariant; 0 without an index): the expected mask is the current
+// marked set marked by k_index_mark itself from an all-zero one into a zeroed
+// scratch mask.  Synchronous.
 abnn_status abnn_debug_index_mask_dirty(abnn_brain* b, uint64_t* words)
 {
     REQUIRE(b && words, "null argument");
     *words = 0;
     ST_TRY(sync_all(b));
-    if (!b->ix.mask) return ABNN_OK;
-    HIP_TRY(launch_index_dirty(b->ix.mask, b->ix.mask_words, reinterpret_cast<unsigned long long*>(b->u64_scratch), b->stream));
+    const IndexState& x = b->ix;
+    if (!x.mask) return ABNN_OK;
+    const DeviceState& d = b->d;
+    DeviceTemp<uint32_t> want, none, next;
+    ST_TRY(want.alloc(x.mask_words));
+    ST_TRY(none.alloc(d.n_bitmap_words));
+    ST_TRY(next.alloc(d.n_bitmap_words, false));
+    if (x.built)  // (never otherwise: the mask goes with the index)
+        HIP_TRY(launch_index_mark(x.marked, none.dev, next.dev, d.n_bitmap_words, d.n_nrn, x.row, x.off, want.dev, d.events,
+                                  x.heavy, x.heavy_chunks, nullptr, nullptr, b->stream));
+    HIP_TRY(launch_index_dirty(x.mask, want.dev, x.mask_words, reinterpret_cast<unsigned long long*>(b->u64_scratch), b->stream));
     return read_words(b, b->u64_scratch, words, 1);
+}
+
+// The event mask's first n_words words (all of it, padding included, when
+// n_words is at least its length; what lies past it in the caller's buffer
+// stays) and likewise the marked set's first n_marked_words, as
+// abnn_debug_bitmap.  Synchronous; an error without an index.
+abnn_status abnn_debug_index_mask_copy(abnn_brain* b, uint32_t* mask_words_out, uint64_t n_words, uint32_t* marked_out,
+                                       uint64_t n_marked_words)
+{
+    REQUIRE(b && (mask_words_out || n_words == 0) && (marked_out || n_marked_words == 0), "null argument");
+    ST_TRY(sync_all(b));
+    REQUIRE(b->ix.built, "abnn_debug_index_mask_copy: no index is built");
+    n_words = std::min<uint64_t>(n_words, b->ix.mask_words);
+    n_marked_words = std::min<uint64_t>(n_marked_words, b->d.n_bitmap_words);
+    if (n_words) HIP_TRY(hipMemcpy(mask_words_out, b->ix.mask, n_words * 4, hipMemcpyDeviceToHost));
+    if (n_marked_words) HIP_TRY(hipMemcpy(marked_out, b->ix.marked, n_marked_words * 4, hipMemcpyDeviceToHost));
+    return ABNN_OK;
+}
+
+// The last mark launch's {neurons entered, neurons left, entries set, entries
+// cleared} (zeros without an index or before its first indexed pass).  Synchronous.
+abnn_status abnn_debug_index_delta(abnn_brain* b, uint64_t out[4])
+{
+    REQUIRE(b && out, "null argument");
+    ST_TRY(sync_all(b));
+    std::vector<uint32_t> v(4 * kDeltaSlots, 0u);
+    if (b->ix.delta) HIP_TRY(hipMemcpy(v.data(), b->ix.delta + b->ix.delta_at, v.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 4; ++i) out[i] = 0;
+    for (size_t i = 0; i < v.size(); ++i) out[i & 3] += v[i];
+    return ABNN_OK;
 }
 
 // ABNN_INDEXED for this handle from now on (0 never, 1 the rule, 2 whenever the index is valid).

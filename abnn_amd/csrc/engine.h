@@ -205,8 +205,8 @@ struct DeviceState {
     uint32_t gate_k;          // events per thread per iteration
     uint32_t fused_max_blocks;  // fused-pass workgroups resident at once (all must be: the look-back)
     uint32_t indexed;         // this fused launch is the mask flavour (index.h; capi.hip run_fused sets it per pass)
-    uint32_t* ev_mask;        // ... its event mask: one bit per event of the sweep's iterations, padded (index_mask_words);
-                              // set by k_index_mark in front of the launch, all-zero again behind it
+    const uint32_t* ev_mask;  // ... its event mask: one bit per event of the sweep's iterations, padded (index_mask_words);
+                              // brought up to this pass's bitmap by k_index_mark in front of the launch, only read by it
 };
 
 struct KernelParams {

@@ -9,13 +9,24 @@
 // is whatever the scatter's atomics made it.  It is valid while the src of
 // records [0, E) and E itself do not change (capi.hip index_invalidate).
 //
-// The mask holds one bit per event.  k_index_mark, launched in front of the
-// pass, ORs the lists of every neuron of this pass's exact recent-spike bitmap
-// into it: afterwards bit e is set iff bitmap[src(e)] is, which is the
-// pre-spike gate itself (brain.metal:73-77), no false positives and no false
-// negatives.  k_gate's mask flavour (kernels.hip) streams the mask where the
-// stream flavour streams the 3-B src codes, and stores zero over what it read,
-// so the mask is all-zero again when the pass ends.
+// The mask holds one bit per event, and the index keeps a marked set beside
+// it, a bitmap over neurons.  The invariant, at every kernel boundary: mask
+// bit e is set iff src(e) is in the marked set.  Both start all-zero when the
+// index is built and go with it (index_invalidate); k_index_mark is their only
+// writer, so passes of other flavours in between leave them alone.
+// k_index_mark, launched in front of an indexed pass, is a delta mark: it
+// compares the marked set with this pass's exact recent-spike bitmap, ORs the
+// lists of the neurons that enter into the mask, AND-NOTs the lists of those
+// that leave out of it, and leaves marked set = bitmap.  Afterwards bit e is
+// set iff bitmap[src(e)] is, which is the pre-spike gate itself
+// (brain.metal:73-77), no false positives and no false negatives.  k_gate's
+// mask flavour (kernels.hip) streams the mask where the stream flavour streams
+// the 3-B src codes, and only reads it.
+//
+// The marked set has two buffers: a launch reads the one and writes the other
+// (a heavy chunk's workgroup reads its neuron's old bit from a word that a
+// light wave of the same launch rewrites), and the host swaps them after an
+// indexed pass, as it rotates the partition's bounds.
 #pragma once
 
 #include "engine.h"
@@ -46,13 +57,21 @@ hipError_t launch_index_build(const SynArrays& syn, uint64_t events, uint64_t n_
 // 0} of heavy[chunks] (info[3]: the fill's cursor).
 hipError_t launch_index_heavy(const uint32_t* row, uint64_t n_nrn, uint4* heavy, uint32_t chunks, uint32_t* info,
                               hipStream_t s);
-// mask |= the events of every neuron set in bitmap[n_words] (this pass's exact
-// bitmap): one launch, the short lists by the waves that hold their neurons'
-// bitmap words, every chunk of the heavy list by a workgroup of its own.
-hipError_t launch_index_mark(const uint32_t* bitmap, uint32_t n_words, uint64_t n_nrn, const uint32_t* row,
-                             const uint32_t* off, uint32_t* mask, uint64_t events, const uint4* heavy, uint32_t chunks,
-                             hipStream_t s);
-// *out (zeroed here) = the non-zero words of mask[words] (abnn_debug_index_mask_dirty).
-hipError_t launch_index_dirty(const uint32_t* mask, uint64_t words, unsigned long long* out, hipStream_t s);
+// The delta mark.  mask |= the events of every neuron of bitmap & ~marked,
+// mask &= ~ the events of every neuron of marked & ~bitmap, marked_next =
+// bitmap (all three of n_words; bitmap: this pass's exact one): one launch, the
+// short lists by the waves that hold their neurons' bitmap words, every chunk
+// of the heavy list by a workgroup of its own.  delta (may be null): the
+// launch adds {neurons entered, neurons left, entries set, entries cleared} to
+// the kDeltaSlots slots of four words (a wave's slot by its number: the sum
+// over the slots is the launch's); delta_next (may be null), as long, is zeroed
+// for the next launch.
+constexpr uint32_t kDeltaSlots = 1024;
+hipError_t launch_index_mark(const uint32_t* bitmap, const uint32_t* marked, uint32_t* marked_next, uint32_t n_words,
+                             uint64_t n_nrn, const uint32_t* row, const uint32_t* off, uint32_t* mask, uint64_t events,
+                             const uint4* heavy, uint32_t chunks, uint32_t* delta, uint32_t* delta_next, hipStream_t s);
+// *out (zeroed here) = the words of mask[words] that differ from want[words] (abnn_debug_index_mask_dirty).
+hipError_t launch_index_dirty(const uint32_t* mask, const uint32_t* want, uint64_t words, unsigned long long* out,
+                              hipStream_t s);
 
 }  // namespace abnn

@@ -6,14 +6,19 @@
 //                one src along a wave's consecutive records add once, runs.h),
 //                an exclusive scan in tiles, then every record's offset to its
 //                neuron's list through a per-neuron cursor.
-//   k_index_mark : per indexed pass, in front of k_gate: the exact recent-spike
-//                bitmap's neurons -> their lists -> the bits of the event mask.
-//                Three dependent round trips (bitmap word, row, off) and one
-//                atomic OR per entry, entries of one wave-instruction that fall
-//                into one mask word merged first.  The lists above kHeavyLen
-//                entries are cut into chunks at build time (k_index_heavy_fill);
-//                each chunk has a workgroup of the same launch.
-//   k_index_dirty : diagnostics, the mask's non-zero words.
+//   k_index_mark : per indexed pass, in front of k_gate: a delta mark.  The
+//                mask persists from pass to pass and stands for the marked set
+//                (index.h); the launch compares it with the pass's exact
+//                recent-spike bitmap, ORs the lists of the neurons that enter
+//                into the mask, AND-NOTs the lists of those that leave out of
+//                it, and leaves marked set = bitmap.  Three dependent round
+//                trips (bitmap words, row, off) and one atomic per entry of a
+//                neuron that changed, entries of one wave-instruction and sign
+//                that fall into one mask word merged first.  The lists above
+//                kHeavyLen entries are cut into chunks at build time
+//                (k_index_heavy_fill); each chunk has a workgroup of the same
+//                launch, which returns when its neuron's bit did not change.
+//   k_index_dirty : diagnostics, the mask's words that differ from another's.
 //
 // The build's two scans read the src streams alone (load_src_pair: 3 B per
 // record).  scan.h's PairLoad is not used for them: it loads the pair's 16 B of
@@ -175,15 +180,23 @@ __global__ __launch_bounds__(256) void k_index_scatter(SynArrays a, uint64_t eve
     }
 }
 
-// Wave-converged: the lanes with act set bit o of the mask.  Entries of one
-// wave-instruction that share a mask word (a neuron whose records lie side by
-// side: the dense input->output block, 32 to a word) would send as many
-// same-address atomics; the lanes that share the first active lane's word are
-// merged into one, for up to kMerge rounds while merging pays (a group of one
-// ends it), as kernels.hip wave_set_next does for the next bitmap.
-__device__ __forceinline__ void wave_mask_or(uint32_t* mask, bool act, uint32_t o)
+// Wave-converged: the lanes with act set (kClear: clear) bit o of the mask.
+// Entries of one wave-instruction that share a mask word (a neuron whose
+// records lie side by side: the dense input->output block, 32 to a word) would
+// send as many same-address atomics; the lanes that share the first active
+// lane's word are merged into one, for up to kMerge rounds while merging pays
+// (a group of one ends it), as kernels.hip wave_set_next does for the next
+// bitmap.  A call merges bits of one sign only: a wave-instruction that holds
+// entries of entering and of leaving neurons takes two calls, and the OR and
+// the AND-NOT that then meet in one word touch distinct bits and commute.
+template <bool kClear>
+__device__ __forceinline__ void wave_mask_apply(uint32_t* mask, bool act, uint32_t o)
 {
     constexpr int kMerge = 8;
+    auto apply = [&](uint32_t word, uint32_t bits) {
+        if constexpr (kClear) (void)__hip_atomic_fetch_and(mask + word, ~bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else (void)__hip_atomic_fetch_or(mask + word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
     const uint32_t lane = threadIdx.x & 63, w = o >> 5, bit = 1u << (o & 31u);
     for (int it = 0; it < kMerge; ++it) {
         const uint64_t m = __ballot(act);
@@ -195,33 +208,66 @@ __device__ __forceinline__ void wave_mask_or(uint32_t* mask, bool act, uint32_t 
         uint32_t bits = same ? bit : 0u;
 #pragma unroll
         for (int x = 32; x > 0; x >>= 1) bits |= __shfl_xor(bits, x, 64);
-        if (lane == lead) (void)__hip_atomic_fetch_or(mask + wl, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == lead) apply(wl, bits);
         act = act && !same;
     }
-    if (act) (void)__hip_atomic_fetch_or(mask + w, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (act) apply(w, bit);
 }
 
-// Light blocks (blockIdx < light): a wave takes kMarkWords words of the bitmap
-// (512 neurons): its set neurons go to an LDS list; up to 256 of them at a
-// time read their row bounds (one round trip for all), wave scans of the list
-// lengths flatten their entries, and the wave reads the entries four
-// wave-instructions at a time (entry j belongs to the last neuron whose prefix
-// is <= j: a search of the 256 prefixes in LDS).  Lists above kHeavyLen
-// entries are skipped here.
+// Entry o of a neuron that enters the marked set (its bit is set) or leaves it
+// (cleared); o past the sweep: neither.
+__device__ __forceinline__ void wave_mask_delta(uint32_t* mask, uint64_t events, uint32_t o, bool leave)
+{
+    const bool valid = o < events;
+    wave_mask_apply<false>(mask, valid && !leave, o);
+    wave_mask_apply<true>(mask, valid && leave, o);
+}
+
+// The delta mark.  `old` is the marked set the mask stands for on entry, `now`
+// this pass's exact bitmap; the launch moves the mask from the one to the
+// other and leaves `next` = now (the host swaps old and next: a heavy
+// workgroup reads old words that a light wave of the same launch would
+// otherwise be overwriting).
+// Light blocks (blockIdx < light): a wave takes kMarkWords words of the two
+// bitmaps (512 neurons) and returns when they are equal.  The neurons of
+// now & ~old (entering) and then those of old & ~now (leaving) go to an LDS
+// list; up to 256 of them at a time read their row bounds (one round trip for
+// all), wave scans of the list lengths flatten their entries, and the wave
+// reads the entries four wave-instructions at a time (entry j belongs to the
+// last neuron whose prefix is <= j: a search of the 256 prefixes in LDS; the
+// neuron's place in the list tells whether it enters or leaves).  Lists above
+// kHeavyLen entries are skipped here.
 // Heavy blocks (the rest, one per chunk of the build's heavy list): the chunk's
-// neuron's bit of the bitmap, then its <= kHeavyChunk entries, four per lane.
+// neuron's bit of both bitmaps -- equal: nothing to do, which is every
+// stimulated input of a steady-state pass -- then its <= kHeavyChunk entries,
+// four per lane.
+// delta (may be null): {neurons entered, neurons left, entries set, entries
+// cleared} of this launch: one atomic instruction per wave that found work,
+// its lanes 0..3 each adding one non-zero counter (so up to four atomics, to
+// one 16-B slot), into the wave's slot of kDeltaSlots.  The slots spread what
+// would otherwise be every wave's atomics to one cache line, which serialise
+// (profiles/ab_index_delta.txt).  The first workgroups zero delta_next, the
+// next launch's block.
 constexpr uint32_t kMarkWaves = 4, kMarkWords = 16, kMarkBatch = 256;
 
-__global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* bitmap, uint32_t n_words, uint32_t n_nrn,
-                                                                const uint32_t* row, const uint32_t* off, uint32_t* mask,
-                                                                uint64_t events, const uint4* heavy, uint32_t light)
+__global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* now, const uint32_t* old, uint32_t* next,
+                                                                uint32_t n_words, uint32_t n_nrn, const uint32_t* row,
+                                                                const uint32_t* off, uint32_t* mask, uint64_t events,
+                                                                const uint4* heavy, uint32_t light, uint32_t* delta,
+                                                                uint32_t* delta_next)
 {
     __shared__ uint16_t s_n[kMarkWaves][kMarkWords * 32];
     __shared__ uint32_t s_beg[kMarkWaves][kMarkBatch], s_pre[kMarkWaves][kMarkBatch];
     const uint32_t lane = threadIdx.x & 63, wid = wave_uniform(threadIdx.x >> 6);
+    if (delta_next)
+        for (uint32_t i = blockIdx.x * (kMarkWaves * 64) + threadIdx.x; i < 4 * kDeltaSlots; i += gridDim.x * (kMarkWaves * 64))
+            delta_next[i] = 0u;
+    if (delta) delta += 4u * ((blockIdx.x * kMarkWaves + wid) & (kDeltaSlots - 1u));
     if (blockIdx.x >= light) {  // workgroup-uniform
         const uint4 it = heavy[blockIdx.x - light];  // {neuron, first entry, entries, 0}
-        if (((bitmap[it.x >> 5] >> (it.x & 31u)) & 1u) == 0u) return;
+        const uint32_t was = (old[it.x >> 5] >> (it.x & 31u)) & 1u, is = (now[it.x >> 5] >> (it.x & 31u)) & 1u;
+        if (was == is) return;
+        const bool leave = was != 0u;
         uint32_t o[4];
 #pragma unroll
         for (uint32_t u = 0; u < 4; ++u) {
@@ -229,18 +275,27 @@ __global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* 
             o[u] = j < it.z ? off[it.y + j] : 0xFFFFFFFFu;
         }
 #pragma unroll
-        for (uint32_t u = 0; u < 4; ++u) wave_mask_or(mask, o[u] < events, o[u]);
+        for (uint32_t u = 0; u < 4; ++u) wave_mask_delta(mask, events, o[u], leave);
+        if (delta && threadIdx.x == 0) atomicAdd(delta + (leave ? 3 : 2), it.z);
         return;
     }
     const uint32_t w0 = (blockIdx.x * kMarkWaves + wid) * kMarkWords;
     if (w0 >= n_words) return;  // wave-uniform
-    const uint32_t word = lane < kMarkWords && w0 + lane < n_words ? bitmap[w0 + lane] : 0u;
-    const uint32_t cnt = (uint32_t)__builtin_popcount(word), inc = wave_incl_scan(cnt);
-    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)inc, 63);
-    if (total == 0) return;
-    uint32_t q = inc - cnt;
-    for (uint32_t m = word; m; m &= m - 1u) s_n[wid][q++] = (uint16_t)(lane * 32u + (uint32_t)__builtin_ctz(m));
+    const bool mine = lane < kMarkWords && w0 + lane < n_words;
+    const uint32_t wnow = mine ? now[w0 + lane] : 0u, wold = mine ? old[w0 + lane] : 0u;
+    if (mine) next[w0 + lane] = wnow;
+    if (__ballot(wnow != wold) == 0) return;
+    const uint32_t went = wnow & ~wold, wlev = wold & ~wnow;
+    const uint32_t ce = (uint32_t)__builtin_popcount(went), ie = wave_incl_scan(ce);
+    const uint32_t cl = (uint32_t)__builtin_popcount(wlev), il = wave_incl_scan(cl);
+    const uint32_t n_ent = (uint32_t)__builtin_amdgcn_readlane((int)ie, 63);
+    const uint32_t total = n_ent + (uint32_t)__builtin_amdgcn_readlane((int)il, 63);
+    uint32_t q = ie - ce;
+    for (uint32_t m = went; m; m &= m - 1u) s_n[wid][q++] = (uint16_t)(lane * 32u + (uint32_t)__builtin_ctz(m));
+    q = n_ent + il - cl;
+    for (uint32_t m = wlev; m; m &= m - 1u) s_n[wid][q++] = (uint16_t)(lane * 32u + (uint32_t)__builtin_ctz(m));
     wave_lds_sync();
+    uint32_t set = 0, clr = 0;  // this lane's neurons' entries
     for (uint32_t c0 = 0; c0 < total; c0 += kMarkBatch) {  // wave-uniform
         uint32_t b[4], len[4];
 #pragma unroll
@@ -251,6 +306,8 @@ __global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* 
             const uint32_t e = vn ? row[n + 1] : 0u;
             b[u] = vn ? row[n] : 0u;
             len[u] = e > b[u] && e - b[u] <= kHeavyLen ? e - b[u] : 0u;
+            set += i < n_ent ? len[u] : 0u;
+            clr += i < n_ent ? 0u : len[u];
         }
         uint32_t T = 0;
 #pragma unroll
@@ -263,6 +320,7 @@ __global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* 
         wave_lds_sync();
         for (uint32_t j0 = 0; j0 < T; j0 += 256) {  // wave-uniform
             uint32_t o[4];
+            bool leave[4];
 #pragma unroll
             for (uint32_t u = 0; u < 4; ++u) {
                 const uint32_t j = j0 + u * 64 + lane;
@@ -274,11 +332,18 @@ __global__ __launch_bounds__(kMarkWaves * 64) void k_index_mark(const uint32_t* 
                     else hi = mid;
                 }
                 o[u] = j < T ? off[s_beg[wid][lo] + (j - s_pre[wid][lo])] : 0xFFFFFFFFu;
+                leave[u] = c0 + lo >= n_ent;
             }
 #pragma unroll
-            for (uint32_t u = 0; u < 4; ++u) wave_mask_or(mask, o[u] < events, o[u]);
+            for (uint32_t u = 0; u < 4; ++u) wave_mask_delta(mask, events, o[u], leave[u]);
         }
         wave_lds_sync();  // the next batch overwrites s_beg / s_pre
+    }
+    if (delta) {  // lanes 0..3: one atomic instruction
+        set = wave_add(set);
+        clr = wave_add(clr);
+        const uint32_t v = lane == 0 ? n_ent : lane == 1 ? total - n_ent : lane == 2 ? set : clr;
+        if (lane < 4 && v) atomicAdd(delta + lane, v);
     }
 }
 
@@ -296,10 +361,11 @@ __global__ __launch_bounds__(256) void k_index_heavy_fill(const uint32_t* row, u
         heavy[slot + c] = make_uint4((uint32_t)n, b + c * kHeavyChunk, min(kHeavyChunk, len - c * kHeavyChunk), 0u);
 }
 
-__global__ __launch_bounds__(256) void k_index_dirty(const uint32_t* mask, uint64_t words, unsigned long long* out)
+__global__ __launch_bounds__(256) void k_index_dirty(const uint32_t* mask, const uint32_t* want, uint64_t words,
+                                                     unsigned long long* out)
 {
     uint32_t n = 0;
-    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (uint64_t)gridDim.x * 256) n += mask[i] != 0u;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (uint64_t)gridDim.x * 256) n += mask[i] != want[i];
     n = wave_add(n);
     if ((threadIdx.x & 63) == 0 && n) atomicAdd(out, (unsigned long long)n);
 }
@@ -333,23 +399,24 @@ hipError_t launch_index_heavy(const uint32_t* row, uint64_t n_nrn, uint4* heavy,
     return hipGetLastError();
 }
 
-hipError_t launch_index_mark(const uint32_t* bitmap, uint32_t n_words, uint64_t n_nrn, const uint32_t* row,
-                             const uint32_t* off, uint32_t* mask, uint64_t events, const uint4* heavy, uint32_t chunks,
-                             hipStream_t s)
+hipError_t launch_index_mark(const uint32_t* bitmap, const uint32_t* marked, uint32_t* marked_next, uint32_t n_words,
+                             uint64_t n_nrn, const uint32_t* row, const uint32_t* off, uint32_t* mask, uint64_t events,
+                             const uint4* heavy, uint32_t chunks, uint32_t* delta, uint32_t* delta_next, hipStream_t s)
 {
     if (n_words == 0) return hipSuccess;
     const uint32_t per = kMarkWaves * kMarkWords, light = (n_words + per - 1) / per;
-    hipLaunchKernelGGL(k_index_mark, dim3(light + chunks), dim3(kMarkWaves * 64), 0, s, bitmap, n_words, (uint32_t)n_nrn, row,
-                       off, mask, events, heavy, light);
+    hipLaunchKernelGGL(k_index_mark, dim3(light + chunks), dim3(kMarkWaves * 64), 0, s, bitmap, marked, marked_next, n_words,
+                       (uint32_t)n_nrn, row, off, mask, events, heavy, light, delta, delta_next);
     return hipGetLastError();
 }
 
-hipError_t launch_index_dirty(const uint32_t* mask, uint64_t words, unsigned long long* out, hipStream_t s)
+hipError_t launch_index_dirty(const uint32_t* mask, const uint32_t* want, uint64_t words, unsigned long long* out,
+                              hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(out, 0, 8, s);
     if (e != hipSuccess) return e;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(2048, (words + 255) / 256));
-    hipLaunchKernelGGL(k_index_dirty, dim3(grid), dim3(256), 0, s, mask, words, out);
+    hipLaunchKernelGGL(k_index_dirty, dim3(grid), dim3(256), 0, s, mask, want, words, out);
     return hipGetLastError();
 }
 

@@ -23,9 +23,10 @@
 //                brain.metal:110-113, clock brain.metal:129).  The next pass's
 //                bitmap and filter are built on the way (set-only atomics).
 //   k_gate<..., kFused, kLean, !kShard, kMask> : the same pass over the
-//                per-pass event mask that k_index_mark (index.hip) set from
-//                the exact bitmap, instead of over the src stream (the indexed
-//                pass; capi.hip run_fused chooses per pass).
+//                event mask that k_index_mark (index.hip) brought up to the
+//                exact bitmap, instead of over the src stream; the mask is
+//                only read (the indexed pass; capi.hip run_fused
+//                chooses per pass).
 //   k_gate<..., !kFused> + k_apply : the two-kernel pass (sharded passes,
 //                random-edge mode, ABNN_FUSED=0): the gate writes per-chunk
 //                survivor slots, k_apply walks the budget over them, updates
@@ -1369,9 +1370,10 @@ __device__ __forceinline__ void set_priority(uint32_t p)
 // wave's slice of the 64 KiB of LDS the filter image does not need.  A 1-KiB
 // piece is scanned from the lanes' own 16-B words (event order (lane, bit));
 // a piece with more hits than the stage has room for block by block from the
-// slice, in the (lane, k) order with the quarter path.  The wave stores zero
-// over the non-zero 16-B words of its own range, so the mask is clean again
-// when the pass ends.  It stages {offset} alone (refrac_chunk kMask).
+// slice, in the (lane, k) order with the quarter path.  The flavour only reads
+// the mask: k_index_mark keeps it from pass to pass and moves it by the
+// difference of two bitmaps (index.h).  It stages {offset} alone (refrac_chunk
+// kMask).
 template <int BLOCK, int K, int FW, bool kTrack, bool kRandom, bool kFused, bool kLean = false, bool kShard = false,
           bool kMask = false>
 __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
@@ -1538,7 +1540,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     // round of kMaskRoundBytes, ML 16-B loads per lane and round (wave-
     // instruction j reads bytes [1024 j, 1024 j + 1024) of the round); a
     // round is read whole, so past the range's end it holds the next ranges'
-    // bytes (never scanned, never cleared here) and past the sweep's the
+    // bytes (never scanned here) and past the sweep's the
     // mask's padding (index.h).  mrow: the wave's slice of the LDS the filter
     // image does not need.
     constexpr uint32_t BI = IE / 8, RI = kMaskRoundBytes / BI;
@@ -1546,7 +1548,7 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
     static_assert(!kMask || (size_t)FW * sizeof(uint2) >= (size_t)NW * kMaskRoundBytes, "the mask rounds fit the filter's LDS");
     u32x4 mk[ML];
     u32x4* const mrow = reinterpret_cast<u32x4*>(s_fb) + wid * (kMaskRoundBytes / 16);
-    auto mask_at = [&](uint32_t it0) { return reinterpret_cast<u32x4*>(d.ev_mask) + (uint64_t)it0 * (BI / 16); };
+    auto mask_at = [&](uint32_t it0) { return reinterpret_cast<const u32x4*>(d.ev_mask) + (uint64_t)it0 * (BI / 16); };
     auto mask_issue = [&](uint32_t it0) __attribute__((always_inline)) {
         const u32x4* p = mask_at(it0);
 #pragma unroll
@@ -1830,21 +1832,19 @@ __global__ __launch_bounds__(BLOCK) void k_gate(DeviceState d, KernelParams kp)
         const uint8_t* mbytes = reinterpret_cast<const uint8_t*>(mrow);
         constexpr uint32_t PI = 1024 / BI;  // iterations per 1-KiB piece of a round (one 16-B load per lane)
         for (uint32_t r0 = it_begin; r0 < it_end; r0 += RI) {  // wave-uniform
-            // this round's words; the next round's loads next (a load issued
-            // behind a store would wait for it); then zero over the non-zero
-            // 16-B words of this range (a word never straddles an iteration:
-            // BI is a multiple of 16)
+            // this round's words, without the next ranges' bits (a word never
+            // straddles an iteration: BI is a multiple of 16), into the wave's
+            // LDS slice; then the next round's loads.  The mask is only read:
+            // it stays what k_index_mark made it (index.h)
             u32x4 cur[ML];
 #pragma unroll
             for (int j = 0; j < ML; ++j) cur[j] = mk[j];
             if (r0 + RI < it_end) mask_issue(r0 + RI);
-            u32x4* const mp = mask_at(r0);
 #pragma unroll
             for (int j = 0; j < ML; ++j) {
                 // lane L's word of piece j: events 128 L .. 128 L + 127 of the piece, all of one iteration
                 const bool in = r0 + (uint32_t)(j * 1024 + lane * 16) / BI < it_end;
                 if (!in) cur[j] = u32x4{0u, 0u, 0u, 0u};  // the next ranges' bits
-                if ((cur[j].x | cur[j].y | cur[j].z | cur[j].w) != 0u) mp[j * 64 + lane] = u32x4{0u, 0u, 0u, 0u};
                 mrow[j * 64 + lane] = cur[j];  // (the pieces are taken from the wave's LDS slice: one copy of the code below)
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront", "local");

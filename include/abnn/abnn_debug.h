@@ -81,9 +81,23 @@ abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path);
  * build's time.  Not synchronous. */
 #define ABNN_DEBUG_INDEX_WORDS 8
 abnn_status abnn_debug_index_state(abnn_brain* b, uint64_t out[ABNN_DEBUG_INDEX_WORDS], double* build_ms);
-/* The non-zero 32-bit words of the event mask: 0 between passes (the pass
- * clears what it reads), 0 without an index.  Synchronous. */
+/* The 32-bit words of the event mask that differ from what the next indexed
+ * pass expects: bit e set iff src(e) is in the marked set, the bitmap of the
+ * last indexed pass (all-zero after a build).  The expected mask is made by the
+ * mark kernel itself from the marked set.  0 at every kernel boundary, 0
+ * without an index.  Synchronous. */
 abnn_status abnn_debug_index_mask_dirty(abnn_brain* b, uint64_t* words);
+/* The event mask's first n_words 32-bit words (bit e of the mask: event e) and
+ * the marked set's first n_marked_words (bit n: neuron n) to the host; a count
+ * above a buffer's length copies all of it (the mask's padding included) and
+ * leaves the rest of the caller's words as they are, as abnn_debug_bitmap.
+ * Synchronous; an error without an index. */
+abnn_status abnn_debug_index_mask_copy(abnn_brain* b, uint32_t* mask_words_out, uint64_t n_words, uint32_t* marked_out,
+                                       uint64_t n_marked_words);
+/* The last mark launch: out = {neurons that entered the marked set, neurons
+ * that left it, mask bits set, mask bits cleared}.  Zeros before the first
+ * indexed pass since the build.  Synchronous. */
+abnn_status abnn_debug_index_delta(abnn_brain* b, uint64_t out[4]);
 /* ABNN_INDEXED for this handle's following passes: 0 never indexed, 1 the
  * default rule, 2 whenever the index is valid.  Not synchronous. */
 abnn_status abnn_debug_set_indexed(abnn_brain* b, int mode);

@@ -12,6 +12,7 @@ this package is its Python host mirror:
 * :mod:`abnn_amd.reorder` -- the record reorder: config, keys, numpy reference, the inverse of an origin;
 * :mod:`abnn_amd.snapshot` -- device-side snapshots: the Snapshot object, the diff's config, numpy reference and merge;
 * :mod:`abnn_amd.hops` -- reachability: config, numpy reference, the merge of shard planes between steps;
+* :mod:`abnn_amd.components` -- connected components: config, numpy reference, decode, the merge of shard planes;
 * :mod:`abnn_amd.propagate` -- signal propagation: config, numpy reference, rescale, merge of shard results, branching ratio;
 * :mod:`abnn_amd.graph` -- the graph builder: blocks, weight laws, spec, validator, numpy reference;
 * :mod:`abnn_amd.spikes` -- the spike recorder: config, pass dtype, numpy reference, raster split;
@@ -19,8 +20,8 @@ this package is its Python host mirror:
 * :mod:`abnn_amd.shard` -- synapse-shard data parallelism over torch.distributed;
 * :mod:`abnn_amd.configs` -- the BASELINE.json workloads.
 """
-from . import census, corr, degree, edit, graph, hops, propagate, reorder, select, snapshot, spikes
-from ._lib import (AbnnError, CensusConfig, CorrConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, PropagateConfig, ReorderConfig, SelectConfig, SpikesConfig,
+from . import census, components, corr, degree, edit, graph, hops, propagate, reorder, select, snapshot, spikes
+from ._lib import (AbnnError, CensusConfig, ComponentsConfig, CorrConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, PropagateConfig, ReorderConfig, SelectConfig, SpikesConfig,
                    default_params, device_count,
                    load as load_library)
 from .brain import SYN_DTYPE, Brain, visited_events
@@ -30,7 +31,7 @@ from .snapshot import Snapshot
 from .spikes import SPIKE_PASS_DTYPE
 
 __all__ = [
-    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "CorrConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "PropagateConfig", "ReorderConfig", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
-    "SelectConfig", "Snapshot", "SpikesConfig", "Workload", "default_engine_config", "census", "corr", "default_params", "degree",
+    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "ComponentsConfig", "CorrConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "PropagateConfig", "ReorderConfig", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
+    "SelectConfig", "Snapshot", "SpikesConfig", "Workload", "default_engine_config", "census", "components", "corr", "default_params", "degree",
     "device_count", "edit", "graph", "hops", "load_library", "propagate", "reorder", "select", "snapshot", "spikes", "visited_events",
 ]

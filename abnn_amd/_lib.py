@@ -229,6 +229,24 @@ class SnapshotInfo(C.Structure):
     _fields_ = [("captures", C.c_uint64), ("n_syn", C.c_uint64), ("scalars", Scalars), ("bytes", C.c_uint64)]
 
 
+COMP_WEIGHT, COMP_SIZES = 1, 2
+COMP_HEADER_WORDS = 8
+COMP_SIZE_BINS = 32
+COMP_NONE = 0xFFFFFFFF
+COMP_BEGIN, COMP_LINK, COMP_FLATTEN, COMP_CLOSE = 0, 1, 2, 3
+
+
+class ComponentsConfig(C.Structure):
+    """abnn_components_config -- the neuron range, the flags and the weight bounds of a connected-components labelling."""
+
+    _fields_ = [
+        ("first", C.c_uint32), ("count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
 HOPS_MAX = 1024
 HOPS_REVERSE, HOPS_WEIGHT = 1, 2
 HOPS_HEADER_WORDS = 8
@@ -431,6 +449,12 @@ SIGNATURES = [
     ("abnn_hops_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _VP]),
     ("abnn_hops_step_enqueue", C.c_int, [_VP, C.POINTER(HopsConfig), C.c_uint32, _VP, _VP]),
     ("abnn_hops", C.c_int, [_VP, C.POINTER(HopsConfig), _VP, _U64]),
+    ("abnn_components_words", C.c_uint64, [C.POINTER(ComponentsConfig), _U64]),
+    ("abnn_components_enqueue", C.c_int, [_VP, C.POINTER(ComponentsConfig), _VP, _VP]),
+    ("abnn_components_step_enqueue", C.c_int, [_VP, C.POINTER(ComponentsConfig), C.c_uint32, _VP, _VP]),
+    ("abnn_components_merge_enqueue", C.c_int, [_VP, C.POINTER(ComponentsConfig), _VP, C.c_uint32, _VP, _VP]),
+    ("abnn_components", C.c_int, [_VP, C.POINTER(ComponentsConfig), _VP, _U64]),
+    ("abnn_components_host", C.c_int, [_VP, _U64, C.POINTER(ComponentsConfig), _U64, _VP, _U64]),
     ("abnn_propagate_words", C.c_uint64, [C.POINTER(PropagateConfig), _U64]),
     ("abnn_propagate_enqueue", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _VP]),
     ("abnn_propagate", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _U64]),
@@ -528,7 +552,9 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_reorder_words", "abnn_reorder_enqueue", "abnn_reorder", "abnn_reorder_release",
                    "abnn_reorder_host",
                    "abnn_propagate_words", "abnn_propagate_enqueue", "abnn_propagate", "abnn_propagate_rescale_enqueue",
-                   "abnn_propagate_iterate_enqueue", "abnn_propagate_host", "abnn_propagate_rescale_host")
+                   "abnn_propagate_iterate_enqueue", "abnn_propagate_host", "abnn_propagate_rescale_host",
+                   "abnn_components_words", "abnn_components_enqueue", "abnn_components_step_enqueue",
+                   "abnn_components_merge_enqueue", "abnn_components", "abnn_components_host")
 
 _lib = None
 
@@ -561,6 +587,7 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_raw_wave_clock", C.c_int, [_VP, C.c_uint64, _U32, _U32, C.POINTER(C.c_uint64), C.c_uint64, _VP]),
     ("abnn_debug_live_allocations", C.c_uint64, []),
     ("abnn_debug_set_propagate_path", C.c_int, [_VP, C.c_int]),
+    ("abnn_debug_set_components_path", C.c_int, [_VP, C.c_int]),
     ("abnn_debug_index_state", C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("abnn_debug_index_mask_dirty", C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     ("abnn_debug_set_indexed", C.c_int, [_VP, C.c_int]),

@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import census as _census
+from . import components as _components
 from . import corr as _corr
 from . import degree as _degree
 from . import edit as _edit
@@ -385,6 +386,45 @@ class Brain:
         device memory at ``out_ptr``: the sharded caller's path, which merges
         the ranks' planes (hops.merge_planes) between two steps."""
         call("abnn_hops_step_enqueue", self._h, C.byref(cfg), int(step), int(out_ptr), _stream_ptr(stream))
+
+    def components(self, neurons=None, weights=None, sizes: bool = False) -> dict:
+        """Connected components on the device (abnn_components):
+        the weakly connected components of this handle's records over the
+        neuron range ``neurons`` = (first, count) (None: every neuron);
+        ``weights`` = (w_lo, w_hi) follows only records with w_lo <= w < w_hi,
+        ``sizes`` also returns the per-neuron component size; the rule is in
+        abnn.h.  Returns records, neurons, followed, components, largest,
+        largest_label, singletons, gave_up, ``bins`` (np.uint64), ``labels``
+        (np.uint32: the smallest neuron id of the component, components.NONE
+        outside the range) and with ``sizes`` the plane ``sizes``
+        (components.decode)."""
+        n_nrn = self.n_neuron()
+        cfg = _components.config(neurons, weights, sizes, n_nrn)
+        words = int(self._lib.abnn_components_words(C.byref(cfg), n_nrn))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_components", self._h, C.byref(cfg), _ptr(out), words)  # an invalid config fails here
+        return _components.decode(out, cfg, n_nrn)
+
+    def components_enqueue(self, cfg: _lib.ComponentsConfig, out_ptr: int, stream=None) -> None:
+        """Enqueue a whole labelling (BEGIN, LINK, FLATTEN, CLOSE) into device
+        memory at ``out_ptr`` (abnn_components_words(cfg, N_NRN) u64) on
+        ``stream``; nothing synchronises after the handle's first call.
+        Decode with components.decode."""
+        call("abnn_components_enqueue", self._h, C.byref(cfg), int(out_ptr), _stream_ptr(stream))
+
+    def components_step_enqueue(self, cfg: _lib.ComponentsConfig, step: int, out_ptr: int, stream=None) -> None:
+        """Enqueue one step (components.BEGIN / LINK / FLATTEN / CLOSE) of a
+        labelling in the device memory at ``out_ptr``: the sharded caller's path."""
+        call("abnn_components_step_enqueue", self._h, C.byref(cfg), int(step), int(out_ptr), _stream_ptr(stream))
+
+    def components_merge_enqueue(self, cfg: _lib.ComponentsConfig, planes_ptr: int, n_planes: int, out_ptr: int,
+                                 stream=None) -> None:
+        """Enqueue the shard merge: ``planes_ptr`` is device memory holding
+        ``n_planes`` label planes one after the other (each 2 * ((N_NRN + 1) //
+        2) u32, as a result holds it); every neuron of the range is united
+        with its label in each of them, in the plane at ``out_ptr``."""
+        call("abnn_components_merge_enqueue", self._h, C.byref(cfg), int(planes_ptr), int(n_planes), int(out_ptr),
+             _stream_ptr(stream))
 
     def propagate(self, x, inputs=None, outputs=None, reverse: bool = False, fire_p: bool = False, weights=None) -> dict:
         """Signal propagation on the device (abnn_propagate):

@@ -23,6 +23,7 @@
 #include "snapshot.h"
 #include "graph.h"
 #include "hops.h"
+#include "components.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -144,6 +145,10 @@ struct abnn_brain {
     uint32_t* hops_bitmap = nullptr; // abnn_hops_*: the frontier bitmap, N_NRN bits (its first call)
     uint64_t* hops_out = nullptr;    // abnn_hops's device result, grown to the largest one asked
     uint64_t hops_cap = 0;
+    CompScratch comp;                // abnn_components_*: the size counters, the settled map, the sample's word (its first call)
+    uint32_t comp_path = 0;          // ... LINK: 0 the record count chooses, 1 never the settled map, 2 always (abnn_debug_set_components_path)
+    uint64_t* comp_out = nullptr;    // abnn_components's device result, grown to the largest one asked
+    uint64_t comp_cap = 0;
     uint32_t graph_blocks = 0;       // abnn_build_graph: the most workgroups of its launch (64 per CU; ABNN_GRAPH_BLOCKS)
     bool graph_nt = false;           // ... with non-temporal stores (ABNN_GRAPH_NT=1)
     uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
@@ -1992,6 +1997,112 @@ abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_
     ST_TRY(b->pool.grow(&b->hops_out, &b->hops_cap, words));
     ST_TRY(hops_steps(b, cfg, b->hops_out, b->stream));
     return read_words(b, b->hops_out, out_host, words);
+}
+
+/* ---- connected components (components.hip) --------------------- */
+
+uint64_t abnn_components_words(const abnn_components_config* cfg, uint64_t n_nrn) { return components_words(cfg, n_nrn); }
+
+namespace {
+
+constexpr const char* kCompConfig =
+    "components: count >= 1 and the range inside N_NRN, no unknown flags, reserved 0, "
+    "w_lo / w_hi +0 without WEIGHT, with it no NaN bound and w_lo < w_hi";
+
+// The checks of a search on handle b, then its scratch (the first call
+// allocates it, all or nothing: that one may synchronise the device).
+abnn_status components_check(abnn_brain* b, const abnn_components_config* cfg, const uint64_t* out_dev)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 7u) == 0, "components: out_dev must be 8-byte aligned");
+    REQUIRE(components_config_ok(cfg, b->n_nrn), kCompConfig);
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // no memset: CLOSE zeroes the counters, LINK writes every word of the map and the sample's words before it reads them
+    if (!b->comp.counts)
+        ST_TRY(b->pool.alloc_all({raw(&b->comp.counts, 2 * components_plane_words(b->n_nrn)),
+                                  raw(&b->comp.settled, comp_settled_words(b->n_nrn)), raw(&b->comp.major, 2)}));
+    return ABNN_OK;
+}
+
+abnn_status components_step(abnn_brain* b, const abnn_components_config* cfg, uint32_t step, uint64_t* out_dev, hipStream_t s)
+{
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_components_step(b->d.syn, b->dims.n_syn, *cfg, b->n_nrn, step, out_dev, b->comp, b->comp_path,
+                                   (uint32_t)b->cus, s));
+    return ABNN_OK;
+}
+
+abnn_status components_steps(abnn_brain* b, const abnn_components_config* cfg, uint64_t* out_dev, hipStream_t s)
+{
+    for (uint32_t step : {ABNN_COMP_BEGIN, ABNN_COMP_LINK, ABNN_COMP_FLATTEN, ABNN_COMP_CLOSE})
+        ST_TRY(components_step(b, cfg, step, out_dev, s));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_components_enqueue(abnn_brain* b, const abnn_components_config* cfg, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(components_check(b, cfg, out_dev));
+    return components_steps(b, cfg, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_components_step_enqueue(abnn_brain* b, const abnn_components_config* cfg, uint32_t step, uint64_t* out_dev,
+                                         void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(components_check(b, cfg, out_dev));
+    REQUIRE(step <= ABNN_COMP_CLOSE, "components: a step is ABNN_COMP_BEGIN, LINK, FLATTEN or CLOSE");
+    return components_step(b, cfg, step, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_components_merge_enqueue(abnn_brain* b, const abnn_components_config* cfg, const uint32_t* planes_dev,
+                                          uint32_t n_planes, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev && planes_dev, "null argument");
+    REQUIRE(n_planes >= 1, "components: a merge takes at least one plane");
+    REQUIRE((reinterpret_cast<uintptr_t>(planes_dev) & 3u) == 0, "components: planes_dev must be 4-byte aligned");
+    ST_TRY(components_check(b, cfg, out_dev));
+    HIP_TRY(launch_components_merge(*cfg, b->n_nrn, planes_dev, n_planes, out_dev, (uint32_t)b->cus, pick(b, stream)));
+    return ABNN_OK;
+}
+
+abnn_status abnn_components(abnn_brain* b, const abnn_components_config* cfg, uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    ST_TRY(components_check(b, cfg, nullptr));
+    REQUIRE(words == components_words(cfg, b->n_nrn), "abnn_components: words must equal abnn_components_words(cfg, N_NRN)");
+    ST_TRY(sync_all(b));
+    ST_TRY(b->pool.grow(&b->comp_out, &b->comp_cap, words, false));
+    ST_TRY(components_steps(b, cfg, b->comp_out, b->stream));
+    ST_TRY(read_words(b, b->comp_out, out_host, words));
+    if (out_host[7] != 0) {
+        set_err("abnn_components: a bounded loop gave up, code " + std::to_string(out_host[7]) +
+                " (1 the walk to a root, 2 the hook): the result is invalid");
+        return ABNN_ERR_HIP;
+    }
+    return ABNN_OK;
+}
+
+abnn_status abnn_components_host(const abnn_synapse* records, uint64_t n, const abnn_components_config* cfg, uint64_t n_nrn,
+                                 uint64_t* out, uint64_t words)
+{
+    REQUIRE(cfg && out && (records || n == 0), "null argument");
+    REQUIRE(components_config_ok(cfg, n_nrn), kCompConfig);
+    REQUIRE(words == components_words(cfg, n_nrn), "abnn_components_host: words must equal abnn_components_words(cfg, n_nrn)");
+    components_host(*cfg, n_nrn, records, n, out);
+    return ABNN_OK;
+}
+
+// Diagnostics (not part of abnn.h): pin the LINK step of the handle's component searches.
+abnn_status abnn_debug_set_components_path(abnn_brain* b, int path)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(path >= 0 && path <= 2, "abnn_debug_set_components_path: 0 auto, 1 never the settled map, 2 always");
+    b->comp_path = (uint32_t)path;
+    return ABNN_OK;
 }
 
 /* ---- signal propagation (propagate.hip) ----------------------- */

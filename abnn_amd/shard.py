@@ -534,6 +534,42 @@ class ShardedBrain:
         got[0] = int(records.item())
         return _hops.decode(got, cfg, n_nrn)
 
+    def components(self, neurons=None, weights=None, sizes: bool = False) -> dict:
+        """Brain.components over every shard's records (collective: every rank
+        calls it at the same point and gets the whole graph's result).  Every
+        rank labels its own edges (BEGIN, LINK, FLATTEN); a rank's label plane
+        is a spanning forest of that rank's connectivity, so ONE all-gather of
+        the planes and their merge on every rank (components_merge_enqueue,
+        then FLATTEN, CLOSE) gives the whole graph's components.  Words 0
+        (records) and 2 (followed) are summed over the ranks."""
+        from . import components as _comp
+
+        torch, dev = self._torch, self.xchg.device
+        n_nrn = self.brain.n_neuron()
+        cfg = _comp.config(neurons, weights, sizes, n_nrn)
+        words = _comp.n_words(cfg, n_nrn)
+        if not words:
+            raise ValueError("components: invalid config")
+        pw = (n_nrn + 1) // 2
+        out = torch.zeros(words, dtype=torch.int64, device=dev)
+        stream = torch.cuda.current_stream(dev)
+        for step in (_comp.BEGIN, _comp.LINK, _comp.FLATTEN):
+            self.brain.components_step_enqueue(cfg, step, out.data_ptr(), stream)
+        mine = out[_comp.PLANE_AT:_comp.PLANE_AT + pw]
+        planes = torch.empty(self.comm.world * pw, dtype=torch.int64, device=dev)
+        self.comm.all_gather(planes, mine.contiguous())
+        self.brain.components_merge_enqueue(cfg, planes.data_ptr(), self.comm.world, out.data_ptr(), stream)
+        for step in (_comp.FLATTEN, _comp.CLOSE):
+            self.brain.components_step_enqueue(cfg, step, out.data_ptr(), stream)
+        own = out[torch.tensor([0, 2], device=dev)].clone()
+        self.comm.all_reduce_sum(own)
+        got = out.cpu().numpy().view(np.uint64)
+        got[0], got[2] = int(own[0].item()), int(own[1].item())
+        res = _comp.decode(got, cfg, n_nrn)
+        if res["gave_up"]:
+            raise RuntimeError(f"components: a bounded loop gave up, code {res['gave_up']}")
+        return res
+
     def _propagate_merged(self, cfg, x, out, stream):
         """One collective step: this rank's propagation of the device plane
         ``x`` into ``out``, then words 0..3 and y summed over the ranks (exact:

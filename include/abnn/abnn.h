@@ -904,6 +904,115 @@ abnn_status abnn_hops_step_enqueue(abnn_brain* b, const abnn_hops_config* cfg, u
  * N_NRN)).  Its device result stays with the handle until abnn_brain_destroy. */
 abnn_status abnn_hops(abnn_brain* b, const abnn_hops_config* cfg, uint64_t* out_host, uint64_t words);
 
+/* ---- connected components: is it still one network -----------
+ * The weakly connected components of the handle's local records [0, n_syn) over
+ * a neuron range R = [first, first + count), on the device, without moving the
+ * records to the host: one streaming pass over the records with a lock-free
+ * union-find in a one-u32-per-neuron label plane.
+ * Followed records.  Record k < n_syn is FOLLOWED when it is live (dst !=
+ * 0xFFFFFFFF), src and dst are both in R (R lies inside [0, N_NRN), so nothing
+ * outside the plane is ever indexed, also for records written through
+ * abnn_state_ptrs that were never validated) and, with ABNN_COMP_WEIGHT, w >=
+ * w_lo && w < w_hi as single fp32 comparisons (NaN is never followed; the bounds
+ * rules are abnn_select's).  A followed record joins src and dst; the direction
+ * is ignored and a self-loop joins nothing.  Records at or past n_syn are never
+ * read.
+ * Result: 8 + 32 + (N_NRN + 1) / 2 u64 words, with ABNN_COMP_SIZES (N_NRN + 1) /
+ * 2 more:
+ *   0 the handle's n_syn   1 N_NRN   2 followed records (this handle's)
+ *   3 components: the distinct labels in R (a neuron that no followed record
+ *     touches is a component of size 1)
+ *   4 the size of the largest component   5 its label (the smallest label
+ *     among equally large ones)           6 components of size 1
+ *   7 give-up code: 0 in every correct run (see "Bounded loops")
+ *   8..39   bins[j]: the components whose size s has floor(log2 s) == j
+ *   40 ...  the label plane: N_NRN little-endian u32 (an odd N_NRN is padded with
+ *           one zero entry); entry n is the smallest neuron id of n's
+ *           component, ABNN_COMP_NONE for n outside R
+ *   then, with ABNN_COMP_SIZES, the size plane, laid out likewise: entry n is
+ *           the size of n's component, 0 outside R
+ * Steps.  abnn_components_enqueue is exactly BEGIN, LINK, FLATTEN, CLOSE:
+ *   BEGIN    zero words 0..39; plane[n] = n on R, ABNN_COMP_NONE elsewhere
+ *   LINK     unite the ends of every followed local record; add them to word 2
+ *   FLATTEN  replace every entry in R by the root of its tree
+ *   CLOSE    count the sizes; fill words 0, 1, 3..6, the bins and the size plane
+ * Any sequence BEGIN, (LINK | MERGE)*, FLATTEN, CLOSE is valid: a flattened
+ * plane is again a valid forest, so LINK and MERGE may follow a FLATTEN.  The
+ * plane keeps plane[x] <= x with plane[x] an ancestor of x; the root of a
+ * finished component is its smallest id, so the result is canonical: it depends
+ * on neither the grid nor the order nor the timing, and every word is an integer
+ * (abnn_amd/components.py restates it in numpy).
+ * Bounded loops.  No kernel waits for another workgroup.  A walk to a root
+ * strictly decreases the id, a failed hook returns a strictly smaller id; both
+ * loops also carry a hard cap (`count` steps, 2 x `count` retries).  A lane
+ * that reaches it stores a non-zero code in word 7 (1 the walk, 2 the hook) and
+ * stops; abnn_components then returns ABNN_ERR_HIP with the code in
+ * abnn_last_error.
+ * Shards.  A shard holds some of the edges.  A sharded caller runs BEGIN, LINK,
+ * FLATTEN on every rank, all-gathers the label planes, and runs
+ * abnn_components_merge_enqueue of all of them on every rank, then FLATTEN,
+ * CLOSE.  One exchange suffices: a rank's label plane is a spanning forest of
+ * that rank's connectivity.  Every rank then holds the whole graph's words 1,
+ * 3..7, bins and planes; words 0 and 2 are the rank's own.
+ * Scratch.  The size counters (used when SIZES is off) and the settled map (a
+ * bit per neuron that LINK keeps for the neurons already in the majority tree,
+ * so that a record between two of them is skipped without a walk) stay with the
+ * handle: the FIRST components call on a handle allocates them, all or nothing
+ * (ABNN_ERR_OOM), and may synchronise the device; abnn_brain_destroy frees them.
+ * Two calls on one handle enqueued on different streams must be ordered by the
+ * caller.  The calls write no record, no neuron state, no mark and no bitmap of
+ * the passes.
+ * Strongly connected components are out of scope; the strong component of ONE
+ * seed is the intersection of a forward and a reverse abnn_hops from it.      */
+#define ABNN_COMP_WEIGHT   1u   /* follow a record only if w_lo <= w && w < w_hi */
+#define ABNN_COMP_SIZES    2u   /* also return the per-neuron component-size plane */
+#define ABNN_COMP_HEADER_WORDS 8
+#define ABNN_COMP_SIZE_BINS    32
+#define ABNN_COMP_NONE     0xFFFFFFFFu
+/* step values */
+#define ABNN_COMP_BEGIN 0u
+#define ABNN_COMP_LINK 1u
+#define ABNN_COMP_FLATTEN 2u
+#define ABNN_COMP_CLOSE 3u
+typedef struct abnn_components_config {   /* 32 bytes */
+    uint32_t first, count;   /* the neuron range R = [first, first+count), count >= 1 */
+    uint32_t flags;
+    float    w_lo, w_hi;     /* as abnn_hops_config: +0.0f unless WEIGHT */
+    uint32_t reserved[3];    /* 0 */
+} abnn_components_config;
+/* The result's words for a brain of n_nrn neurons, or 0 for an invalid config:
+ * null, count == 0, a range that ends above n_nrn, unknown flag bits, a
+ * reserved word that is not 0, a non-zero w_lo or w_hi without WEIGHT, a NaN
+ * bound or w_lo >= w_hi with it, n_nrn == 0 or >= 2^32.                        */
+uint64_t    abnn_components_words(const abnn_components_config* cfg, uint64_t n_nrn);
+/* Enqueue only: BEGIN, LINK, FLATTEN, CLOSE in stream order on `stream`, into
+ * out_dev (DEVICE memory, 8-byte aligned, abnn_components_words(cfg, N_NRN)
+ * u64); nothing synchronises after the handle's first components call, so it
+ * can sit between passes and between abnn_engine_run calls.  ABNN_ERR_INVALID:
+ * a null argument, a misaligned out_dev, a config that is invalid for the
+ * handle's N_NRN, a handle whose records are invalid.  n_syn == 0 is valid:
+ * every neuron of R is a component of its own.                                */
+abnn_status abnn_components_enqueue(abnn_brain* b, const abnn_components_config* cfg, uint64_t* out_dev, void* stream);
+/* One step (ABNN_COMP_BEGIN / LINK / FLATTEN / CLOSE) in out_dev; also
+ * ABNN_ERR_INVALID for any other step value.                                  */
+abnn_status abnn_components_step_enqueue(abnn_brain* b, const abnn_components_config* cfg, uint32_t step, uint64_t* out_dev, void* stream);
+/* The shard merge, enqueue only: unites n with planes[p][n] for every n in R
+ * and every p < n_planes in out_dev's plane.  planes_dev is DEVICE memory:
+ * n_planes label planes one after the other, each as a result holds it (2 *
+ * ((N_NRN + 1) / 2) u32, the pad entry included) -- what an all-gather of the
+ * ranks' planes leaves.  An entry that is ABNN_COMP_NONE or not in R is skipped:
+ * nothing is indexed from it.  Also ABNN_ERR_INVALID for a null planes_dev and
+ * for n_planes == 0.                                                          */
+abnn_status abnn_components_merge_enqueue(abnn_brain* b, const abnn_components_config* cfg, const uint32_t* planes_dev, uint32_t n_planes, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (==
+ * abnn_components_words(cfg, N_NRN)).  Its device result stays with the handle
+ * until abnn_brain_destroy.  ABNN_ERR_HIP when word 7 is not 0.               */
+abnn_status abnn_components(abnn_brain* b, const abnn_components_config* cfg, uint64_t* out_host, uint64_t words);
+/* The rule on the host, without a device or a handle, over interchange records
+ * of a brain of n_nrn neurons; out holds `words` u64 (==
+ * abnn_components_words(cfg, n_nrn)).                                          */
+abnn_status abnn_components_host(const abnn_synapse* records, uint64_t n, const abnn_components_config* cfg, uint64_t n_nrn, uint64_t* out, uint64_t words);
+
 /* ---- signal propagation: W.x and the branching ratio ----------
  * The handle's local records [0, n_syn) used as the sparse matrix they are: one
  * streaming pass y[kout] += c(w) * x[kin] on the device, in integers, without

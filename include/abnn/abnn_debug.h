@@ -74,6 +74,12 @@ uint64_t abnn_debug_live_allocations(void);
  * Not synchronous. */
 abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path);
 
+/* The LINK step of the handle's following component searches (abnn_components_*):
+ * 0 = the settled map when the handle holds enough records per neuron for it
+ * to pay (the default), 1 = never (every followed record walks the plane), 2 =
+ * always.  The result's words do not depend on it.  Not synchronous. */
+abnn_status abnn_debug_set_components_path(abnn_brain* b, int path);
+
 /* The indexed fused pass: out = {index built (0/1), its entries,
  * its largest degree, the last pass was indexed (0/1), indexed passes so far,
  * consecutive eligible passes since the records last changed, ABNN_INDEXED in

@@ -168,6 +168,35 @@ struct HopsView {
     }
 };
 
+// A view of a connected-components result (abnn.h abnn_components: the header,
+// the bins, the label plane and, with ABNN_COMP_SIZES, the size plane); it does
+// not own the words.
+struct ComponentsView {
+    const uint64_t* words = nullptr;
+    bool has_sizes = false;
+    ComponentsView(const uint64_t* w, const abnn_components_config& cfg) : words(w), has_sizes(cfg.flags & ABNN_COMP_SIZES) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t neurons() const { return words[1]; }
+    uint64_t followed() const { return words[2]; }
+    uint64_t components() const { return words[3]; }
+    uint64_t largest() const { return words[4]; }
+    uint64_t largest_label() const { return words[5]; }
+    uint64_t singletons() const { return words[6]; }
+    uint64_t gave_up() const { return words[7]; }
+    // bins()[j], j < ABNN_COMP_SIZE_BINS: the components whose size s has floor(log2 s) == j
+    const uint64_t* bins() const { return words + ABNN_COMP_HEADER_WORDS; }
+    // labels()[n], n < neurons(): the smallest neuron id of n's component, ABNN_COMP_NONE outside the range
+    const uint32_t* labels() const
+    {
+        return reinterpret_cast<const uint32_t*>(words + ABNN_COMP_HEADER_WORDS + ABNN_COMP_SIZE_BINS);
+    }
+    // sizes()[n]: the size of n's component, 0 outside the range; null without ABNN_COMP_SIZES
+    const uint32_t* sizes() const
+    {
+        return has_sizes ? labels() + 2 * ((neurons() + 1) / 2) : nullptr;
+    }
+};
+
 // A view of a propagation result (abnn.h abnn_propagate: the header and y); it
 // does not own the words.
 struct PropagateView {
@@ -710,6 +739,31 @@ public:
     {
         check(abnn_snapshot_diff_enqueue(h_, then.handle(), now ? now->handle() : nullptr, &cfg, out_dev, stream),
               "abnn_snapshot_diff_enqueue");
+    }
+    // Connected components on the device (abnn_components; the rule is in
+    // abnn.h): the result's words, to be read through a ComponentsView.
+    std::vector<uint64_t> components(const abnn_components_config& cfg) const
+    {
+        const uint64_t words = abnn_components_words(&cfg, n_neuron());
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_components(h_, &cfg, w.data(), words), "abnn_components");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_components_words(&cfg, n_neuron()) u64.
+    void components_enqueue(const abnn_components_config& cfg, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_components_enqueue(h_, &cfg, out_dev, stream), "abnn_components_enqueue");
+    }
+    // One step (ABNN_COMP_BEGIN / LINK / FLATTEN / CLOSE): the sharded caller's path.
+    void components_step_enqueue(const abnn_components_config& cfg, uint32_t step, uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_components_step_enqueue(h_, &cfg, step, out_dev, stream), "abnn_components_step_enqueue");
+    }
+    // The shard merge: planes_dev holds n_planes label planes one after the other (device memory).
+    void components_merge_enqueue(const abnn_components_config& cfg, const uint32_t* planes_dev, uint32_t n_planes,
+                                  uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_components_merge_enqueue(h_, &cfg, planes_dev, n_planes, out_dev, stream), "abnn_components_merge_enqueue");
     }
     // Reachability on the device (abnn_hops; the rule is in abnn.h): the
     // result's words, to be read through a HopsView.

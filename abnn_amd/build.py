@@ -2,6 +2,8 @@
 
 * ``build_hip()``    : hipcc --offload-arch=gfx950 -> abnn_amd/libabnn_hip.so
 * ``build_oracle()`` : gcc -> oracle/liboracle.so (test infrastructure)
+* ``build_reference()`` : clang++ -> oracle/_ref/libref_kernel.so, oracle/_ref/ref_driver (the reference's
+  kernel file and driver classes compiled in place by oracle/ref_recipe/; test infrastructure, never committed)
 * ``build_cpp_example()`` : g++ -> tests/cpp/brain_cpp_test (C++ Brain API over the C-ABI)
 * ``build_learn_test()``  : g++ -> tests/cpp/learn_test (device-resident learning loop vs the oracle)
 * ``build_census_test()`` : g++ -> tests/cpp/census_test (the synapse census's C++ mirrors)
@@ -94,6 +96,15 @@ COMPONENTS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "components_test.cpp")
 COMPONENTS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "components_test")
 COMPONENTS_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "components_host_test.cpp")
 COMPONENTS_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "components_host_test")
+DRIVER_GRID_HDR = os.path.join(ROOT, "tests", "cpp", "driver_grid.hpp")
+REF_RECIPE = os.path.join(ORACLE_DIR, "ref_recipe")
+REF_OUT = os.path.join(ORACLE_DIR, "_ref")
+REF_LIB = os.path.join(REF_OUT, "libref_kernel.so")
+REF_DRIVER = os.path.join(REF_OUT, "ref_driver")
+REFERENCE_DEFAULT = "/root/reference"  # the read-only checkout (DESIGN.md's citations are relative to it)
+REF_FILES = (os.path.join("core", "kernels", "brain.metal"), os.path.join("core", "output-filter", "rate-filter.h"),
+             os.path.join("stimulus", "functional-dataset.cpp"), os.path.join("stimulus", "functional-dataset.h"),
+             os.path.join("stimulus", "stimulus-provider.h"))
 LEARN_BENCH_SRC =os.path.join(ROOT, "tools", "learn_bench.cpp")
 LEARN_BENCH_BIN = os.path.join(ROOT, "tools", "learn_bench")
 
@@ -177,6 +188,59 @@ def build_oracle(force: bool = False) -> str:
     return ORACLE_LIB
 
 
+def reference_dir() -> str | None:
+    """The reference checkout (ABNN_REFERENCE_DIR, else REFERENCE_DEFAULT) if
+    it holds the files the recipe compiles, else None."""
+    d = os.environ.get("ABNN_REFERENCE_DIR", REFERENCE_DEFAULT)
+    return d if all(os.path.isfile(os.path.join(d, "abnn", "src", f)) for f in REF_FILES) else None
+
+
+def _host_cxx() -> tuple[str, list[str]]:
+    """clang++ (next to hipcc's, or on PATH), else g++: the kernel file's
+    [[buffer(n)]] attributes are unknown to both and ignored."""
+    near = os.path.join(os.path.dirname(os.path.realpath(HIPCC)), "..", "lib", "llvm", "bin", "clang++")
+    for c in (shutil.which("clang++"), near, "/opt/rocm/lib/llvm/bin/clang++"):
+        if c and os.path.exists(c):
+            return c, ["-Wno-unknown-attributes"]
+    return "g++", ["-Wno-attributes"]
+
+
+def built_reference() -> tuple[str, str] | None:
+    """(libref_kernel.so, ref_driver) under oracle/_ref/ if both are there."""
+    return (REF_LIB, REF_DRIVER) if os.path.exists(REF_LIB) and os.path.exists(REF_DRIVER) else None
+
+
+def build_reference(force: bool = False) -> tuple[str, str] | None:
+    """The reference's kernel file and driver classes compiled in place as
+    host C++ (oracle/ref_recipe/: a stand-in metal_stdlib, a C1 harness, a
+    stub brain-engine.h) -> oracle/_ref/libref_kernel.so, oracle/_ref/ref_driver.
+    Test infrastructure; oracle/_ref/ is never committed.  Nothing of the
+    reference is copied or generated: its files are included by path.  Without
+    a checkout (a GPU box) nothing is built or touched: returns what is already
+    there, or None."""
+    ref = reference_dir()
+    if ref is None:
+        return built_reference()
+    src = os.path.join(ref, "abnn", "src")
+    recipe = [os.path.join(REF_RECIPE, f) for f in ("metal_stdlib", "ref_kernel.cpp", "ref_driver.cpp",
+                                                    os.path.join("stub", "brain-engine.h"))]
+    deps = [*recipe, DRIVER_GRID_HDR, *(os.path.join(src, f) for f in REF_FILES)]
+    cxx, quiet = _host_cxx()
+    flags = ["-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", *quiet]
+    os.makedirs(REF_OUT, exist_ok=True)
+    if force or _stale(REF_LIB, deps):
+        tmp = REF_LIB + ".tmp"
+        _run([cxx, *flags, "-fPIC", "-shared", "-I", REF_RECIPE, "-I", src, "-o", tmp,
+              os.path.join(REF_RECIPE, "ref_kernel.cpp")])
+        os.replace(tmp, REF_LIB)
+    if force or _stale(REF_DRIVER, deps):
+        tmp = REF_DRIVER + ".tmp"
+        _run([cxx, *flags, "-I", os.path.join(REF_RECIPE, "stub"), "-I", src, "-I", os.path.join(ROOT, "tests", "cpp"),
+              "-o", tmp, os.path.join(REF_RECIPE, "ref_driver.cpp")])
+        os.replace(tmp, REF_DRIVER)
+    return REF_LIB, REF_DRIVER
+
+
 def build_cpp_example(force: bool = False) -> str | None:
     if not os.path.exists(CPP_TEST_SRC):
         return None
@@ -196,7 +260,7 @@ def build_engine_tests(force: bool = False) -> tuple[str | None, str | None]:
     hdrs = [os.path.join(inc, "abnn", "engine.hpp"), os.path.join(inc, "abnn", "brain.hpp")]
     host = None
     if os.path.exists(ENGINE_HOST_SRC):
-        if force or _stale(ENGINE_HOST_BIN, [ENGINE_HOST_SRC, *hdrs]):
+        if force or _stale(ENGINE_HOST_BIN, [ENGINE_HOST_SRC, DRIVER_GRID_HDR, *hdrs]):
             _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-I", inc,
                   "-o", ENGINE_HOST_BIN, ENGINE_HOST_SRC])
         host = ENGINE_HOST_BIN
@@ -488,6 +552,7 @@ def build_learn_bench(force: bool = False) -> str | None:
 def build_all(force: bool = False) -> None:
     build_hip(force)
     build_oracle(force)
+    build_reference(force)
     build_cpp_example(force)
     build_engine_tests(force)
     build_learn_test(force)

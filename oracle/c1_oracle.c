@@ -3,8 +3,10 @@
  * deterministic schedule C1.  TEST INFRASTRUCTURE ONLY (see c1_oracle.h):
  * the product never links, loads or calls this file.
  *
- * PARITY UNPINNED (no reference tests/fixtures exist and brain.metal cannot be
- * built or run in this image -- DESIGN.md §3).
+ * Pinned to the reference kernel's own text: oracle/ref_recipe/ compiles
+ * brain.metal in place as host C++ and tests/test_reference_kernel.py compares
+ * oracle_pass_serial with it word for word under C1, at the default knobs
+ * (DESIGN.md §3).  Parity with the Metal compiler's output stays unpinned.
  *
  * Build: gcc -O2 -std=c11 -ffp-contract=off -fPIC -shared -pthread
  * (-ffp-contract=off: every fp32 operation rounds on its own, exactly like the
@@ -412,7 +414,8 @@ void oracle_pass_serial(oracle_state* s)
     const uint64_t* L = s->last_fired;             /* pass-start snapshot (C1)       */
     const float R = s->reward, rb = s->rbar;        /* MSL:105-106                    */
     uint32_t budget = p->max_spikes;               /* reset per pass, BR:90          */
-    uint32_t* fired = (uint32_t*)malloc(sizeof(uint32_t) * (p->max_spikes + 1u));
+    /* at most min(budget, E) spikes (sized in 64 bits: a budget of 2^32 - 1 is legal) */
+    uint32_t* fired = (uint32_t*)malloc(sizeof(uint32_t) * ((p->max_spikes < E ? p->max_spikes : E) + 1u));
     uint64_t n_fired = 0;
     int t0_updated = 0;
     const int random = p->mode == ABNN_MODE_RANDOM;
@@ -664,7 +667,7 @@ void oracle_pass_threaded(oracle_state* s, int nthreads)
     thr_job* jobs = (thr_job*)calloc((size_t)nthreads, sizeof(thr_job));
     pthread_t th[256];
     uint64_t per = (E + (uint64_t)nthreads - 1) / (uint64_t)nthreads;
-    int32_t* fired = (int32_t*)calloc(p->max_spikes + 1u, sizeof(int32_t));
+    int32_t* fired = (int32_t*)calloc((p->max_spikes < E ? p->max_spikes : E) + 1u, sizeof(int32_t));
     pend_list pend = {NULL, 0, 0};
     for (int k = 0; k < nthreads; ++k) {
         jobs[k].pend = p->mode == ABNN_MODE_RANDOM ? &pend : NULL;

@@ -2,7 +2,7 @@
 
 TEST INFRASTRUCTURE ONLY: may be imported by tests/, ``__graft_entry__.smoke()``
 and the ``cpu_baseline`` leg of bench.py -- never by the product (abnn_amd/).
-PARITY UNPINNED: see c1_oracle.h and DESIGN.md §3.
+Pinned to the reference kernel's text under C1 (tests/test_reference_kernel.py); see DESIGN.md §3.
 """
 from __future__ import annotations
 

@@ -1,12 +1,23 @@
 // engine_host_test.cpp -- TEST PROGRAM (CPU only): RateFilter and
 // FunctionalDataset of include/abnn/engine.hpp on fixed inputs; the output is
 // compared with an independent numpy restatement in tests/test_engine.py.
+// With the argument "grid": the grid of driver_grid.hpp instead, compared with
+// the same grid run on the reference's own classes (oracle/ref_recipe/
+// ref_driver.cpp, recorded in tests/golden/ref_driver.json).
 #include <abnn/engine.hpp>
 
 #include <cstdio>
+#include <cstring>
 
-int main()
+#include "driver_grid.hpp"
+
+int main(int argc, char** argv)
 {
+    if (argc > 1 && std::strcmp(argv[1], "grid") == 0) {
+        driver_grid::print_all<abnn::RateFilter, abnn::FunctionalDataset>(&abnn::FunctionalDataset::cos_squared,
+                                                                          &abnn::FunctionalDataset::half_sine);
+        return 0;
+    }
     abnn::FunctionalDataset ds(8, 8, 0.0009, 0.5, abnn::FunctionalDataset::cos_squared,
                                abnn::FunctionalDataset::half_sine);
     abnn::RateFilter iir(0.02, false), fir(0.02, true, 5);

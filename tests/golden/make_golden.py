@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.json from the C oracle (serial C1 loop).
 
-PARITY UNPINNED against the reference itself: tjamescouch/abnn ships no tests,
-fixtures or golden vectors, and brain.metal cannot be built or run in this
-image.  These files pin the oracle (regression) and give the
-GPU path a fixed target that does not need the oracle at run time.  Each
+These three are oracle outputs: they pin the oracle against regressions on
+longer runs and on lastVisited tracking, and give the GPU path a fixed target
+that does not need the oracle at run time.  The oracle itself is pinned to the
+reference kernel's own text by tests/golden/ref_case*.json, which
+tests/golden/make_ref_golden.py writes from that text compiled on the host
+(DESIGN.md §3); parity with the Metal compiler's output stays unpinned.  Each
 fixture records, per pass: SHA-256 of the synapse array and of lastFired,
 clock, rBar bits and the pass statistics, plus a sparse sample of records.
 

@@ -96,3 +96,69 @@ def test_driver_gpu_matches_oracle(gpu, passes, win):
     assert r.returncode == 0 and res["ok"], (res, r.stderr[-2000:])
     assert res["windows"] == passes // win
     assert res["spikes"] > 0
+
+
+# ---- against the reference's own classes (oracle/ref_recipe/ref_driver.cpp) ----------------------
+# tests/cpp/driver_grid.hpp: RateFilter at tau 0.02 / 0.05, FIR off and windows of 1, 5 and 20, vectors of 1, 8 and
+# 257 over 45 frames; FunctionalDataset at 8/8 and 256/256 over 2300 frames (the phase passes 1.0).  One harness
+# prints the same document for include/abnn/engine.hpp's classes and for the reference's, floats as bits.
+def _host_grid():
+    host, _ = build_engine_tests()
+    return subprocess.run([host, "grid"], capture_output=True, text=True, check=True).stdout
+
+
+def _golden_grid():
+    import os
+
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_driver.json")) as f:
+        return f.read()
+
+
+def _first_grid_difference(got, want):
+    """Where two grid documents first differ, by stream and frame."""
+    for kind in ("filter", "dataset"):
+        assert len(got[kind]) == len(want[kind]), kind
+        for a, b in zip(got[kind], want[kind]):
+            if a != b:
+                head = {k: v for k, v in b.items() if k in ("tau", "fir", "len", "n")}
+                if kind == "filter":
+                    return f"filter {head}: {a} != {b}"
+                bad = next((x, y) for x, y in zip(a["frames"], b["frames"]) if x != y) if a["frames"] != b["frames"] else (a["time"], b["time"])
+                return f"dataset {head}: {bad[0]} != {bad[1]}"
+    return None
+
+
+def test_grid_document_covers_the_grid():
+    want = json.loads(_golden_grid())
+    assert {(s["tau"], s["fir"], s["len"]) for s in want["filter"]} == \
+        {(t, f, n) for t in (0.02, 0.05) for f in (0, 1, 5, 20) for n in (1, 8, 257)}
+    assert [d["n"] for d in want["dataset"]] == [8, 256]
+    for d in want["dataset"]:
+        assert d["frames"][-1]["f"] == 2299 and any(2220 <= fr["f"] <= 2225 and "in" in fr for fr in d["frames"])
+        assert math.isclose(d["time"], 2300 * 0.0009, rel_tol=1e-12)  # 2300 x 0.00045 = 1.035: the phase passed 1.0
+    for s in want["filter"]:  # the moving average changes the result, and so does its window
+        assert len(s["hash"]) == 7
+    by = {(s["tau"], s["fir"], s["len"]): s["hash"] for s in want["filter"]}
+    assert len({tuple(by[(0.02, f, 8)]) for f in (0, 5, 20)}) == 3 and by[(0.02, 0, 8)] == by[(0.02, 1, 8)]
+
+
+def test_rate_filter_and_dataset_equal_recorded_reference_classes():
+    """include/abnn/engine.hpp's classes against tests/golden/ref_driver.json
+    (what the reference's own classes printed): needs no oracle/_ref/."""
+    got, want = _host_grid(), _golden_grid()
+    assert _first_grid_difference(json.loads(got), json.loads(want)) is None
+    assert got == want
+
+
+def test_rate_filter_and_dataset_equal_live_reference_classes():
+    """... and against oracle/_ref/ref_driver run now, which must also print
+    the committed document (so the fixture stays the reference's output)."""
+    import ref_kernel_helpers as R
+
+    if not R.ref_available():
+        pytest.skip("no reference checkout (ABNN_REFERENCE_DIR) and no oracle/_ref/ to run")
+    from abnn_amd.build import build_reference
+
+    live = subprocess.run([build_reference()[1]], capture_output=True, text=True, check=True).stdout
+    assert _first_grid_difference(json.loads(_host_grid()), json.loads(live)) is None
+    assert live == _golden_grid()

@@ -2,8 +2,9 @@
 
 CPU: the oracle reproduces every fixture (regression pin of the restatement).
 GPU: the HIP path reproduces every fixture pass by pass through the C-ABI,
-without running the oracle.  Parity against the Metal reference itself is
-unpinned."""
+without running the oracle.  These fixtures are oracle outputs; the ones made
+from the reference kernel's own text are tests/golden/ref_*.json
+(tests/test_reference_kernel.py, tests/test_gpu_reference_golden.py)."""
 import hashlib
 import json
 import os
@@ -12,7 +13,8 @@ import numpy as np
 import pytest
 
 HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-CASES = sorted(f[:-5] for f in os.listdir(HERE) if f.endswith(".json"))
+# ref_*.json are the reference-made fixtures, in another format (tests/test_reference_kernel.py)
+CASES = sorted(f[:-5] for f in os.listdir(HERE) if f.endswith(".json") and not f.startswith("ref_"))
 
 
 def sha(a):

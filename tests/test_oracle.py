@@ -1,6 +1,6 @@
 """CPU tests of the oracle: known answers, restatement cross-check, threaded and
-sharded phases vs the serial C1 loop.  (Parity against the reference itself is
-UNPINNED -- DESIGN.md §3.)"""
+sharded phases vs the serial C1 loop.  (The serial loop against the reference
+kernel's own text: tests/test_reference_kernel.py)"""
 import numpy as np
 import pytest
 

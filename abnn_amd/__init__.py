@@ -13,6 +13,7 @@ this package is its Python host mirror:
 * :mod:`abnn_amd.snapshot` -- device-side snapshots: the Snapshot object, the diff's config, numpy reference and merge;
 * :mod:`abnn_amd.hops` -- reachability: config, numpy reference, the merge of shard planes between steps;
 * :mod:`abnn_amd.components` -- connected components: config, numpy reference, decode, the merge of shard planes;
+* :mod:`abnn_amd.matrix` -- the population connectivity matrix: config, built-in bounds, numpy reference, decode, merge of shard results;
 * :mod:`abnn_amd.propagate` -- signal propagation: config, numpy reference, rescale, merge of shard results, branching ratio;
 * :mod:`abnn_amd.graph` -- the graph builder: blocks, weight laws, spec, validator, numpy reference;
 * :mod:`abnn_amd.spikes` -- the spike recorder: config, pass dtype, numpy reference, raster split;
@@ -20,8 +21,8 @@ this package is its Python host mirror:
 * :mod:`abnn_amd.shard` -- synapse-shard data parallelism over torch.distributed;
 * :mod:`abnn_amd.configs` -- the BASELINE.json workloads.
 """
-from . import census, components, corr, degree, edit, graph, hops, propagate, reorder, select, snapshot, spikes
-from ._lib import (AbnnError, CensusConfig, ComponentsConfig, CorrConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, PropagateConfig, ReorderConfig, SelectConfig, SpikesConfig,
+from . import census, components, corr, degree, edit, graph, hops, matrix, propagate, reorder, select, snapshot, spikes
+from ._lib import (AbnnError, CensusConfig, ComponentsConfig, CorrConfig, DegreeConfig, DiffConfig, EditConfig, GraphBlock, GraphSpec, HopsConfig, MatrixConfig, PropagateConfig, ReorderConfig, SelectConfig, SpikesConfig,
                    default_params, device_count,
                    load as load_library)
 from .brain import SYN_DTYPE, Brain, visited_events
@@ -31,7 +32,7 @@ from .snapshot import Snapshot
 from .spikes import SPIKE_PASS_DTYPE
 
 __all__ = [
-    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "ComponentsConfig", "CorrConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "PropagateConfig", "ReorderConfig", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
+    "AbnnError", "Brain", "CONFIGS", "CensusConfig", "ComponentsConfig", "CorrConfig", "DegreeConfig", "DiffConfig", "EditConfig", "GraphBlock", "GraphSpec", "HopsConfig", "LearnEngine", "MatrixConfig", "PropagateConfig", "ReorderConfig", "SPIKE_PASS_DTYPE", "SYN_DTYPE",
     "SelectConfig", "Snapshot", "SpikesConfig", "Workload", "default_engine_config", "census", "components", "corr", "default_params", "degree",
-    "device_count", "edit", "graph", "hops", "load_library", "propagate", "reorder", "select", "snapshot", "spikes", "visited_events",
+    "device_count", "edit", "graph", "hops", "load_library", "matrix", "propagate", "reorder", "select", "snapshot", "spikes", "visited_events",
 ]

@@ -247,6 +247,23 @@ class ComponentsConfig(C.Structure):
     ]
 
 
+MAT_COUNT, MAT_W, MAT_P = 1, 2, 4
+MAT_LABELS, MAT_WEIGHT = 1, 2
+MATRIX_MAX_POPS = 64
+MATRIX_HEADER_WORDS = 16
+
+
+class MatrixConfig(C.Structure):
+    """abnn_matrix_config -- the populations, the planes, the flags and the weight bounds of a connectivity matrix."""
+
+    _fields_ = [
+        ("pops", C.c_uint32), ("what", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("w_lo", C.c_float), ("w_hi", C.c_float),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
 HOPS_MAX = 1024
 HOPS_REVERSE, HOPS_WEIGHT = 1, 2
 HOPS_HEADER_WORDS = 8
@@ -455,6 +472,10 @@ SIGNATURES = [
     ("abnn_components_merge_enqueue", C.c_int, [_VP, C.POINTER(ComponentsConfig), _VP, C.c_uint32, _VP, _VP]),
     ("abnn_components", C.c_int, [_VP, C.POINTER(ComponentsConfig), _VP, _U64]),
     ("abnn_components_host", C.c_int, [_VP, _U64, C.POINTER(ComponentsConfig), _U64, _VP, _U64]),
+    ("abnn_matrix_words", C.c_uint64, [C.POINTER(MatrixConfig)]),
+    ("abnn_matrix_enqueue", C.c_int, [_VP, C.POINTER(MatrixConfig), _VP, _VP, _VP, _VP]),
+    ("abnn_matrix", C.c_int, [_VP, C.POINTER(MatrixConfig), _VP, _VP, _VP, _U64]),
+    ("abnn_matrix_host", C.c_int, [_VP, _U64, C.POINTER(MatrixConfig), _VP, _VP, _U64, C.c_float, _VP, _U64]),
     ("abnn_propagate_words", C.c_uint64, [C.POINTER(PropagateConfig), _U64]),
     ("abnn_propagate_enqueue", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _VP]),
     ("abnn_propagate", C.c_int, [_VP, C.POINTER(PropagateConfig), _VP, _VP, _U64]),
@@ -554,7 +575,8 @@ ABI10_ADDITIONS = ("abnn_comm_group_create", "abnn_comm_group_destroy", "abnn_co
                    "abnn_propagate_words", "abnn_propagate_enqueue", "abnn_propagate", "abnn_propagate_rescale_enqueue",
                    "abnn_propagate_iterate_enqueue", "abnn_propagate_host", "abnn_propagate_rescale_host",
                    "abnn_components_words", "abnn_components_enqueue", "abnn_components_step_enqueue",
-                   "abnn_components_merge_enqueue", "abnn_components", "abnn_components_host")
+                   "abnn_components_merge_enqueue", "abnn_components", "abnn_components_host",
+                   "abnn_matrix_words", "abnn_matrix_enqueue", "abnn_matrix", "abnn_matrix_host")
 
 _lib = None
 
@@ -588,6 +610,7 @@ DEBUG_SIGNATURES = [
     ("abnn_debug_live_allocations", C.c_uint64, []),
     ("abnn_debug_set_propagate_path", C.c_int, [_VP, C.c_int]),
     ("abnn_debug_set_components_path", C.c_int, [_VP, C.c_int]),
+    ("abnn_debug_set_matrix_path", C.c_int, [_VP, C.c_int]),
     ("abnn_debug_index_state", C.c_int, [_VP, C.POINTER(C.c_uint64), C.POINTER(C.c_double)]),
     ("abnn_debug_index_mask_dirty", C.c_int, [_VP, C.POINTER(C.c_uint64)]),
     ("abnn_debug_set_indexed", C.c_int, [_VP, C.c_int]),

@@ -21,6 +21,7 @@ from . import corr as _corr
 from . import degree as _degree
 from . import edit as _edit
 from . import hops as _hops
+from . import matrix as _matrix
 from . import propagate as _propagate
 from . import reorder as _reorder
 from . import select as _select
@@ -425,6 +426,64 @@ class Brain:
         with its label in each of them, in the plane at ``out_ptr``."""
         call("abnn_components_merge_enqueue", self._h, C.byref(cfg), int(planes_ptr), int(n_planes), int(out_ptr),
              _stream_ptr(stream))
+
+    def _matrix_partition(self, bounds, labels, pops):
+        """(P, bounds array or None, labels device pointer or None, keep-alive)
+        of a matrix call.  Neither given: the built-in populations."""
+        if labels is None:
+            if bounds is None:
+                bounds = _matrix.io_bounds(self.n_input(), self.n_output(), self.n_hidden())
+            b = np.ascontiguousarray(bounds, dtype=np.uint32)
+            if b.ndim != 1 or len(b) < 2 or (pops is not None and int(pops) != len(b) - 1):
+                raise ValueError("matrix: bounds holds P + 1 values")
+            return len(b) - 1, b, None, b
+        if bounds is not None or pops is None:
+            raise ValueError("matrix: labels needs pops and no bounds")
+        if isinstance(labels, (int, np.integer)):
+            return int(pops), None, int(labels), None
+        if isinstance(labels, np.ndarray):  # uploaded
+            import torch
+
+            if labels.shape != (self.n_neuron(),):
+                raise ValueError("matrix: labels must hold N_NRN entries")
+            labels = torch.from_numpy(np.ascontiguousarray(labels, dtype=np.uint32).view(np.int32)).to(f"cuda:{self.device}")
+        if labels.element_size() != 4 or labels.numel() < self.n_neuron() or not labels.is_contiguous():
+            raise ValueError("matrix: a labels tensor holds N_NRN contiguous 32-bit entries")
+        return int(pops), None, int(labels.data_ptr()), labels
+
+    def matrix(self, bounds=None, labels=None, pops: Optional[int] = None, what=("count", "w"), weights=None) -> dict:
+        """Population connectivity matrix on the device (abnn_matrix,
+        DESIGN.md §9): for every pair (a, b) of populations the records from a
+        to b (``count``), their summed weights (``w``) and fire probabilities
+        (``p``) in 2**-24 fixed point, in one pass over this handle's records.
+        The partition is ``bounds`` (P + 1 ascending ids; None and no labels:
+        inputs / outputs / hidden, matrix.io_bounds) or ``labels`` with
+        ``pops`` = P: a plane of N_NRN u32 (a torch tensor on this device, a
+        device pointer, or a numpy array that is uploaded), values >= P = no
+        population.  ``weights`` = (w_lo, w_hi) counts only w_lo <= w < w_hi;
+        the rule is in abnn.h.  Returns the header, ``sizes``, the planes and
+        ``density`` (matrix.decode)."""
+        n_pops, b, lab_ptr, keep = self._matrix_partition(bounds, labels, pops)
+        cfg = _matrix.config(n_pops, what, lab_ptr is not None, weights)
+        words = int(self._lib.abnn_matrix_words(C.byref(cfg)))
+        out = np.zeros(max(words, 1), dtype=np.uint64)
+        call("abnn_matrix", self._h, C.byref(cfg), None if b is None else _ptr(b), lab_ptr, _ptr(out), words)
+        del keep
+        return _matrix.decode(out, cfg)  # an invalid config failed above
+
+    def matrix_enqueue(self, cfg: _lib.MatrixConfig, out_ptr: int, bounds=None, labels_ptr: Optional[int] = None,
+                       stream=None) -> None:
+        """Enqueue a connectivity matrix into device memory at ``out_ptr``
+        (abnn_matrix_words(cfg) u64) on ``stream``; nothing synchronises after
+        the handle's first LABELS call.  ``bounds`` (host values, read during
+        the call) or ``labels_ptr`` (device memory, N_NRN u32: e.g. the distance
+        plane inside a hops result), whichever cfg's LABELS flag names.  Decode
+        with matrix.decode."""
+        b = None if bounds is None else np.ascontiguousarray(bounds, dtype=np.uint32)
+        if b is not None and b.shape != (int(cfg.pops) + 1,):
+            raise ValueError("matrix: bounds holds P + 1 values")
+        call("abnn_matrix_enqueue", self._h, C.byref(cfg), None if b is None else _ptr(b),
+             None if labels_ptr is None else int(labels_ptr), int(out_ptr), _stream_ptr(stream))
 
     def propagate(self, x, inputs=None, outputs=None, reverse: bool = False, fire_p: bool = False, weights=None) -> dict:
         """Signal propagation on the device (abnn_propagate):

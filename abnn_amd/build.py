@@ -23,6 +23,8 @@
 * ``build_propagate_test()`` : g++ -> tests/cpp/propagate_test (the propagation's C++ mirrors vs abnn_propagate_host)
 * ``build_components_test()`` : g++ -> tests/cpp/components_test (the connected components' C++ mirrors vs abnn_components_host)
 * ``build_components_host_test()`` : g++ -fsanitize -> tests/cpp/components_host_test (the components' host rule alone, CPU only)
+* ``build_matrix_test()`` : g++ -> tests/cpp/matrix_test (the connectivity matrix's C++ mirrors vs abnn_matrix_host)
+* ``build_matrix_host_test()`` : g++ -fsanitize -> tests/cpp/matrix_host_test (the matrix's host rule alone, CPU only)
 
 All fp32 code is compiled with -ffp-contract=off so that the GPU and the CPU
 oracle round every operation identically (bit-exact weights).
@@ -42,14 +44,14 @@ HIP_SOURCES = [os.path.join(CSRC, "kernels.hip"), os.path.join(CSRC, "capi.hip")
                os.path.join(CSRC, "graph.hip"), os.path.join(CSRC, "hops.hip"), os.path.join(CSRC, "edit.hip"),
                os.path.join(CSRC, "snapshot.hip"), os.path.join(CSRC, "corr.hip"), os.path.join(CSRC, "reorder.hip"),
                os.path.join(CSRC, "propagate.hip"), os.path.join(CSRC, "index.hip"),
-               os.path.join(CSRC, "components.hip")]
+               os.path.join(CSRC, "components.hip"), os.path.join(CSRC, "matrix.hip")]
 HIP_DEPS = HIP_SOURCES + [os.path.join(CSRC, "engine.h"), os.path.join(CSRC, "device.h"),
                           os.path.join(CSRC, "learn.h"), os.path.join(CSRC, "census.h"), os.path.join(CSRC, "spikes.h"),
                           os.path.join(CSRC, "degree.h"), os.path.join(CSRC, "select.h"), os.path.join(CSRC, "graph.h"),
                           os.path.join(CSRC, "hops.h"), os.path.join(CSRC, "edit.h"), os.path.join(CSRC, "snapshot.h"),
                           os.path.join(CSRC, "corr.h"), os.path.join(CSRC, "reorder.h"), os.path.join(CSRC, "scan.h"), os.path.join(CSRC, "pool.h"),
                           os.path.join(CSRC, "propagate.h"), os.path.join(CSRC, "runs.h"), os.path.join(CSRC, "index.h"),
-                          os.path.join(CSRC, "components.h"),
+                          os.path.join(CSRC, "components.h"), os.path.join(CSRC, "matrix.h"),
                           os.path.join(ROOT, "include", "abnn", "abnn.h")]
 LIB = os.path.join(PKG, "libabnn_hip.so")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
@@ -96,6 +98,10 @@ COMPONENTS_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "components_test.cpp")
 COMPONENTS_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "components_test")
 COMPONENTS_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "components_host_test.cpp")
 COMPONENTS_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "components_host_test")
+MATRIX_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "matrix_test.cpp")
+MATRIX_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "matrix_test")
+MATRIX_HOST_TEST_SRC = os.path.join(ROOT, "tests", "cpp", "matrix_host_test.cpp")
+MATRIX_HOST_TEST_BIN = os.path.join(ROOT, "tests", "cpp", "matrix_host_test")
 DRIVER_GRID_HDR = os.path.join(ROOT, "tests", "cpp", "driver_grid.hpp")
 REF_RECIPE = os.path.join(ORACLE_DIR, "ref_recipe")
 REF_OUT = os.path.join(ORACLE_DIR, "_ref")
@@ -536,6 +542,34 @@ def build_components_host_test(force: bool = False, out: str | None = None) -> s
     return target
 
 
+def build_matrix_test(force: bool = False) -> str | None:
+    """Test program of the connectivity matrix's C++ mirrors (Brain::matrix,
+    MatrixView against abnn_matrix_host on the generated graph)."""
+    if not os.path.exists(MATRIX_TEST_SRC):
+        return None
+    inc = os.path.join(ROOT, "include")
+    deps = [MATRIX_TEST_SRC, LIB, *(os.path.join(inc, "abnn", h) for h in ("brain.hpp", "abnn.h"))]
+    if force or _stale(MATRIX_TEST_BIN, deps):
+        _run(["g++", "-O2", "-std=c++17", "-Wall", "-ffp-contract=off", "-pthread", "-I", inc,
+              "-o", MATRIX_TEST_BIN, MATRIX_TEST_SRC, "-L", PKG, "-labnn_hip", "-ldl",
+              f"-Wl,-rpath,{PKG}", "-Wl,-rpath,$ORIGIN/../../abnn_amd"])
+    return MATRIX_TEST_BIN
+
+
+def build_matrix_host_test(force: bool = False, out: str | None = None) -> str | None:
+    """The stand-alone program over the connectivity matrix's host rule
+    (csrc/matrix.h alone: no HIP, no library), with the address and
+    undefined-behaviour sanitizers: a CPU program, run by tests/test_matrix_abi.py."""
+    if not os.path.exists(MATRIX_HOST_TEST_SRC):
+        return None
+    target = out or MATRIX_HOST_TEST_BIN
+    deps = [MATRIX_HOST_TEST_SRC, os.path.join(CSRC, "matrix.h"), os.path.join(ROOT, "include", "abnn", "abnn.h")]
+    if force or out or _stale(target, deps):
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+              "-fno-sanitize-recover=all", "-o", target, MATRIX_HOST_TEST_SRC])
+    return target
+
+
 def build_learn_bench(force: bool = False) -> str | None:
     """The timing driver of tools/learn_bench.py (host-driven loop vs device-resident loop)."""
     if not os.path.exists(LEARN_BENCH_SRC):
@@ -569,6 +603,8 @@ def build_all(force: bool = False) -> None:
     build_propagate_test(force)
     build_components_test(force)
     build_components_host_test(force)
+    build_matrix_test(force)
+    build_matrix_host_test(force)
     build_learn_bench(force)
 
 

@@ -24,6 +24,7 @@
 #include "graph.h"
 #include "hops.h"
 #include "components.h"
+#include "matrix.h"
 #include "engine.h"
 #include "learn.h"
 #include "spikes.h"
@@ -149,6 +150,10 @@ struct abnn_brain {
     uint32_t comp_path = 0;          // ... LINK: 0 the record count chooses, 1 never the settled map, 2 always (abnn_debug_set_components_path)
     uint64_t* comp_out = nullptr;    // abnn_components's device result, grown to the largest one asked
     uint64_t comp_cap = 0;
+    uint8_t* mat_pack = nullptr;     // abnn_matrix_*: the label plane packed to one byte per neuron (its first LABELS call)
+    uint32_t mat_path = 0;           // ... 0 auto, 1..4 runs / atomics x packed / direct (abnn_debug_set_matrix_path)
+    uint64_t* mat_out = nullptr;     // abnn_matrix's device result, grown to the largest one asked
+    uint64_t mat_cap = 0;
     uint32_t graph_blocks = 0;       // abnn_build_graph: the most workgroups of its launch (64 per CU; ABNN_GRAPH_BLOCKS)
     bool graph_nt = false;           // ... with non-temporal stores (ABNN_GRAPH_NT=1)
     uint32_t select_blocks = 0;      // ... the most workgroups of its count and emit launches (4 per CU; ABNN_SELECT_BLOCKS)
@@ -2102,6 +2107,100 @@ abnn_status abnn_debug_set_components_path(abnn_brain* b, int path)
     REQUIRE(b, "null argument");
     REQUIRE(path >= 0 && path <= 2, "abnn_debug_set_components_path: 0 auto, 1 never the settled map, 2 always");
     b->comp_path = (uint32_t)path;
+    return ABNN_OK;
+}
+
+/* ---- population connectivity matrix (matrix.hip) ---------------- */
+
+uint64_t abnn_matrix_words(const abnn_matrix_config* cfg) { return matrix_words(cfg); }
+
+namespace {
+
+constexpr const char* kMatConfig =
+    "matrix: pops in 1..64, what a non-empty subset of COUNT | W | P, no unknown flags, reserved 0, "
+    "w_lo / w_hi +0 without WEIGHT, with it no NaN bound and w_lo < w_hi";
+constexpr const char* kMatPartition =
+    "matrix: exactly one of bounds / labels is set, the one the LABELS flag names";
+constexpr const char* kMatBounds = "matrix: bounds[0] <= bounds[1] <= ... <= bounds[P] <= N_NRN";
+
+// the checks that need no handle
+abnn_status matrix_args_check(const abnn_matrix_config* cfg, const uint32_t* bounds, const uint32_t* labels, uint64_t n_nrn)
+{
+    REQUIRE(cfg, "null argument");
+    REQUIRE(matrix_config_ok(cfg), kMatConfig);
+    const bool lab = cfg->flags & ABNN_MAT_LABELS;
+    REQUIRE(lab ? (labels && !bounds) : (bounds && !labels), kMatPartition);
+    REQUIRE(lab || matrix_bounds_ok(bounds, cfg->pops, n_nrn), kMatBounds);
+    return ABNN_OK;
+}
+
+// The checks of a matrix on handle b, then its scratch (the first LABELS call
+// allocates it: that one may synchronise the device).
+abnn_status matrix_check(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds, const uint32_t* labels_dev,
+                         const uint64_t* out_dev)
+{
+    REQUIRE(b && cfg, "null argument");
+    REQUIRE((reinterpret_cast<uintptr_t>(out_dev) & 7u) == 0, "matrix: out_dev must be 8-byte aligned");
+    REQUIRE((reinterpret_cast<uintptr_t>(labels_dev) & 3u) == 0, "matrix: labels_dev must be 4-byte aligned");
+    ST_TRY(matrix_args_check(cfg, bounds, labels_dev, b->n_nrn));
+    REQUIRE(!b->records_invalid, kRecordsInvalid);
+    HIP_TRY(hipSetDevice(b->device));
+    // no memset: k_matrix_pack writes every byte before the scan reads it
+    if ((cfg->flags & ABNN_MAT_LABELS) && !b->mat_pack) ST_TRY(b->pool.alloc_all({raw(&b->mat_pack, b->n_nrn)}));
+    return ABNN_OK;
+}
+
+abnn_status matrix_launch(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds, const uint32_t* labels_dev,
+                          uint64_t* out_dev, hipStream_t s)
+{
+    // the host knows n_syn: structural updates synchronise
+    HIP_TRY(launch_matrix(b->d.syn, b->dims.n_syn, *cfg, bounds, labels_dev, b->n_nrn, b->kp.base_scale, b->mat_pack,
+                          b->mat_path, out_dev, (uint32_t)b->cus, s));
+    return ABNN_OK;
+}
+
+}  // namespace
+
+abnn_status abnn_matrix_enqueue(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds_host,
+                                const uint32_t* labels_dev, uint64_t* out_dev, void* stream)
+{
+    REQUIRE(b && cfg && out_dev, "null argument");
+    ST_TRY(matrix_check(b, cfg, bounds_host, labels_dev, out_dev));
+    return matrix_launch(b, cfg, bounds_host, labels_dev, out_dev, pick(b, stream));
+}
+
+abnn_status abnn_matrix(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds_host, const uint32_t* labels_dev,
+                        uint64_t* out_host, uint64_t words)
+{
+    REQUIRE(b && cfg && out_host, "null argument");
+    // every refusal comes before the scratch: a refused call allocates nothing and synchronises nothing
+    ST_TRY(matrix_args_check(cfg, bounds_host, labels_dev, b->n_nrn));
+    REQUIRE(words == matrix_words(cfg), "abnn_matrix: words must equal abnn_matrix_words(cfg)");
+    ST_TRY(matrix_check(b, cfg, bounds_host, labels_dev, nullptr));
+    ST_TRY(sync_all(b));
+    ST_TRY(b->pool.grow(&b->mat_out, &b->mat_cap, words, false));
+    ST_TRY(matrix_launch(b, cfg, bounds_host, labels_dev, b->mat_out, b->stream));
+    return read_words(b, b->mat_out, out_host, words);
+}
+
+abnn_status abnn_matrix_host(const abnn_synapse* records, uint64_t n, const abnn_matrix_config* cfg, const uint32_t* bounds,
+                             const uint32_t* labels, uint64_t n_nrn, float base_scale, uint64_t* out, uint64_t words)
+{
+    REQUIRE(cfg && out && (records || n == 0), "null argument");
+    REQUIRE(n_nrn >= 1 && n_nrn < (1ull << 32), "matrix: n_nrn in 1 .. 2^32 - 1");
+    ST_TRY(matrix_args_check(cfg, bounds, labels, n_nrn));
+    REQUIRE(words == matrix_words(cfg), "abnn_matrix_host: words must equal abnn_matrix_words(cfg)");
+    matrix_host(*cfg, bounds, labels, n_nrn, base_scale, records, n, out);
+    return ABNN_OK;
+}
+
+// Diagnostics (not part of abnn.h): pin the kernel path of the handle's matrices.
+abnn_status abnn_debug_set_matrix_path(abnn_brain* b, int path)
+{
+    REQUIRE(b, "null argument");
+    REQUIRE(path >= 0 && path <= 4,
+            "abnn_debug_set_matrix_path: 0 auto, 1 runs + packed, 2 runs + direct, 3 atomics + packed, 4 atomics + direct");
+    b->mat_path = (uint32_t)path;
     return ABNN_OK;
 }
 

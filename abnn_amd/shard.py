@@ -570,6 +570,28 @@ class ShardedBrain:
             raise RuntimeError(f"components: a bounded loop gave up, code {res['gave_up']}")
         return res
 
+    def matrix(self, bounds=None, labels=None, pops=None, what=("count", "w"), weights=None) -> dict:
+        """Brain.matrix over every shard's records (collective: every rank
+        calls it at the same point with the same partition and gets the whole
+        graph's result): the local result, then words 0..8 and the planes
+        summed as int64 (all_reduce_sum; the sums wrap as the device's do).
+        Words 9..11 and the sizes are the same on every rank and are not
+        summed.  That is matrix.merge."""
+        from . import matrix as _matrix
+
+        torch = self._torch
+        local = self.brain.matrix(bounds, labels, pops, what, weights)
+        words = _matrix.to_words(local)
+        n_pops = int(local["pops"])
+        cfg = _matrix.config(n_pops, sum(bit for k, bit in (("count", 1), ("w", 2), ("p", 4)) if k in local))
+        at = _matrix.SIZES_AT + n_pops
+        summed = np.concatenate([words[:9], words[at:]])
+        t = torch.from_numpy(summed.view(np.int64).copy()).to(self.xchg.device)
+        self.comm.all_reduce_sum(t)
+        got = t.cpu().numpy().view(np.uint64)
+        words[:9], words[at:] = got[:9], got[9:]
+        return _matrix.decode(words, cfg)
+
     def _propagate_merged(self, cfg, x, out, stream):
         """One collective step: this rank's propagation of the device plane
         ``x`` into ``out``, then words 0..3 and y summed over the ranks (exact:

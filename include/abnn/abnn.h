@@ -1013,6 +1013,98 @@ abnn_status abnn_components(abnn_brain* b, const abnn_components_config* cfg, ui
  * abnn_components_words(cfg, n_nrn)).                                          */
 abnn_status abnn_components_host(const abnn_synapse* records, uint64_t n, const abnn_components_config* cfg, uint64_t n_nrn, uint64_t* out, uint64_t words);
 
+/* ---- population connectivity matrix: who talks to whom --------
+ * For a partition of the neurons into P populations, the count and the summed
+ * weight of the records from population a to population b, for every pair, in
+ * ONE streaming pass over the handle's local records [0, n_syn), on the device.
+ * Records at or past n_syn are never read.
+ * Partition.  A partition maps a neuron id to a population 0 .. P - 1 or to
+ * none, 1 <= P <= ABNN_MATRIX_MAX_POPS.
+ *   BOUNDS (default): P + 1 HOST u32 values bounds[0] <= bounds[1] <= ... <=
+ *     bounds[P] <= N_NRN; pop(n) = j iff bounds[j] <= n < bounds[j + 1]; n <
+ *     bounds[0] or n >= bounds[P] is none.  Empty populations (equal
+ *     neighbours) are legal.  The values are read during the call.
+ *   LABELS (ABNN_MAT_LABELS): a DEVICE plane of N_NRN little-endian u32 -- the
+ *     layout of the abnn_hops distance plane and of the abnn_components label
+ *     plane, so a pointer into either result is a valid argument.  pop(n) =
+ *     labels[n] when n < N_NRN and labels[n] < P, otherwise none
+ *     (ABNN_HOPS_UNREACHED, ABNN_COMP_NONE and any value >= P are none).  An id
+ *     >= N_NRN on a live record (such records reach a handle through
+ *     abnn_state_ptrs) is never used as an index.
+ * Each record is classified in this order:
+ *   1. dst == 0xFFFFFFFF: a tombstone (word 1).
+ *   2. with ABNN_MAT_WEIGHT, a record that fails w >= w_lo && w < w_hi (single
+ *      fp32 comparisons; NaN never passes; the bounds rules are abnn_select's)
+ *      is out of band (word 6).
+ *   3. otherwise a = pop(src), b = pop(dst): both set: COUNTED (word 2), cell
+ *      a * P + b; only b set: word 3; only a set: word 4; neither: word 5.
+ * Planes: one u64 per cell, row-major, one plane per bit of `what` in increasing
+ * bit order.
+ *   ABNN_MAT_COUNT  the counted records of the cell
+ *   ABNN_MAT_W      the two's-complement sum modulo 2^64 of the degree census's
+ *                   term: a record with fabsf(w) < 128 is summable, its term is
+ *                   q = (int32_t)(w * 16777216.0f); a counted record that is
+ *                   not summable adds nothing and is counted in word 7
+ *   ABNN_MAT_P      the same with c = (w * w) * base_scale in place of w (two
+ *                   fp32 operations: abnn_propagate's coefficient with FIRE_P
+ *                   and its summability test): the expected spikes per visit,
+ *                   the coupling the traversal sees; not summable: word 8
+ * Result: ABNN_MATRIX_HEADER_WORDS + P + planes * P * P u64:
+ *   0 scanned (n_syn)   1 tombstones   2 counted   3 src unassigned
+ *   4 dst unassigned    5 both unassigned   6 out of band
+ *   7 / 8 counted records not summable for W / P (0 unless the plane is asked)
+ *   9 P   10 N_NRN   11 assigned neurons   12..15 zero
+ *   16 .. 16 + P - 1   sizes[j]: the neurons of population j (BOUNDS: bounds[j +
+ *                      1] - bounds[j]; LABELS: counted on the device)
+ *   then the planes.
+ * Words 1 + 2 + 3 + 4 + 5 + 6 == word 0, the COUNT plane sums to word 2, the
+ * sizes sum to word 11.  Every word is an integer sum: the result depends on
+ * neither the grid nor the order nor the timing (abnn_amd/matrix.py restates it
+ * in numpy).
+ * Shards.  Words 0..8 and the planes of the shards' results add up to the whole
+ * graph's; words 9..11 and the sizes are the same on every rank.
+ * Scratch.  A LABELS call packs the plane into one byte per neuron (N_NRN bytes)
+ * that stay with the handle: the FIRST LABELS call on a handle allocates them
+ * (ABNN_ERR_OOM) and may synchronise the device; abnn_brain_destroy frees them.
+ * Two LABELS calls on one handle enqueued on different streams must be ordered
+ * by the caller.  The calls write no record, no neuron state and no bitmap of
+ * the passes, and no workgroup waits for another.                             */
+#define ABNN_MAT_COUNT   1u   /* `what`: the planes */
+#define ABNN_MAT_W       2u
+#define ABNN_MAT_P       4u
+#define ABNN_MAT_LABELS  1u   /* `flags`: the partition is a device label plane */
+#define ABNN_MAT_WEIGHT  2u   /* count a record only if w_lo <= w && w < w_hi */
+#define ABNN_MATRIX_MAX_POPS     64
+#define ABNN_MATRIX_HEADER_WORDS 16
+typedef struct abnn_matrix_config {   /* 32 bytes */
+    uint32_t pops;           /* P */
+    uint32_t what;           /* a non-empty subset of COUNT | W | P */
+    uint32_t flags;          /* ABNN_MAT_LABELS, ABNN_MAT_WEIGHT */
+    float    w_lo, w_hi;     /* as abnn_hops_config: +0.0f unless WEIGHT */
+    uint32_t reserved[3];    /* 0 */
+} abnn_matrix_config;
+/* The result's words, or 0 for an invalid config: null, pops outside 1..64,
+ * `what` empty or with unknown bits, unknown flag bits, a reserved word that is
+ * not 0, a non-zero w_lo or w_hi without WEIGHT, a NaN bound or w_lo >= w_hi
+ * with it.                                                                    */
+uint64_t    abnn_matrix_words(const abnn_matrix_config* cfg);
+/* Enqueue only, in stream order on `stream`, into out_dev (DEVICE memory, 8-byte
+ * aligned, abnn_matrix_words(cfg) u64); nothing synchronises after the handle's
+ * first LABELS call, so it can sit between passes and between abnn_engine_run
+ * calls.  Exactly one of bounds_host / labels_dev is non-null, the one the
+ * LABELS flag names.  ABNN_ERR_INVALID: a null argument, a misaligned out_dev or
+ * labels_dev (4 bytes), an invalid config, a partition argument that contradicts
+ * the flag, decreasing bounds, bounds[P] > N_NRN, a handle whose records are
+ * invalid.  n_syn == 0 is valid: the sizes only.                              */
+abnn_status abnn_matrix_enqueue(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds_host, const uint32_t* labels_dev, uint64_t* out_dev, void* stream);
+/* Synchronous convenience: out_host holds `words` u64 (== abnn_matrix_words(cfg)).
+ * Its device result stays with the handle until abnn_brain_destroy.           */
+abnn_status abnn_matrix(abnn_brain* b, const abnn_matrix_config* cfg, const uint32_t* bounds_host, const uint32_t* labels_dev, uint64_t* out_host, uint64_t words);
+/* The rule on the host, without a device or a handle, over interchange records
+ * of a brain of n_nrn neurons (1 <= n_nrn < 2^32); `labels` is a HOST plane of
+ * n_nrn u32 here; base_scale is abnn_params.base_scale (the P plane's).       */
+abnn_status abnn_matrix_host(const abnn_synapse* records, uint64_t n, const abnn_matrix_config* cfg, const uint32_t* bounds, const uint32_t* labels, uint64_t n_nrn, float base_scale, uint64_t* out, uint64_t words);
+
 /* ---- signal propagation: W.x and the branching ratio ----------
  * The handle's local records [0, n_syn) used as the sparse matrix they are: one
  * streaming pass y[kout] += c(w) * x[kin] on the device, in integers, without

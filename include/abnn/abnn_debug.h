@@ -80,6 +80,15 @@ abnn_status abnn_debug_set_propagate_path(abnn_brain* b, int path);
  * always.  The result's words do not depend on it.  Not synchronous. */
 abnn_status abnn_debug_set_components_path(abnn_brain* b, int path);
 
+/* The kernel path of the handle's following connectivity matrices
+ * (abnn_matrix_*): how a record's cell is added -- run aggregation along the
+ * wave (a wave in one cell adds once), or one LDS atomic per record -- and where
+ * a LABELS scan reads a population: the handle's packed byte plane or the
+ * caller's u32 plane.  0 = the default (runs, packed), 1 = runs + packed, 2 =
+ * runs + direct, 3 = atomics + packed, 4 = atomics + direct.  The result's
+ * words do not depend on it.  Not synchronous. */
+abnn_status abnn_debug_set_matrix_path(abnn_brain* b, int path);
+
 /* The indexed fused pass: out = {index built (0/1), its entries,
  * its largest degree, the last pass was indexed (0/1), indexed passes so far,
  * consecutive eligible passes since the records last changed, ABNN_INDEXED in

@@ -197,6 +197,41 @@ struct ComponentsView {
     }
 };
 
+// A view of a connectivity-matrix result (abnn.h abnn_matrix: the header, the
+// sizes and one P x P plane per bit of `what`); it does not own the words.
+struct MatrixView {
+    const uint64_t* words = nullptr;
+    uint32_t what = 0;
+    MatrixView(const uint64_t* w, const abnn_matrix_config& cfg) : words(w), what(cfg.what) {}
+    uint64_t records() const { return words[0]; }
+    uint64_t tombstones() const { return words[1]; }
+    uint64_t counted() const { return words[2]; }
+    uint64_t src_unassigned() const { return words[3]; }
+    uint64_t dst_unassigned() const { return words[4]; }
+    uint64_t unassigned() const { return words[5]; }
+    uint64_t out_of_band() const { return words[6]; }
+    uint64_t skipped_w() const { return words[7]; }
+    uint64_t skipped_p() const { return words[8]; }
+    uint64_t pops() const { return words[9]; }
+    uint64_t neurons() const { return words[10]; }
+    uint64_t assigned() const { return words[11]; }
+    // the neurons of population j
+    uint64_t size(uint64_t j) const { return words[ABNN_MATRIX_HEADER_WORDS + j]; }
+    // the plane of `bit` (one of ABNN_MAT_COUNT / W / P), P x P row-major; null when it was not asked
+    const uint64_t* plane(uint32_t bit) const
+    {
+        if (!(what & bit)) return nullptr;
+        uint64_t before = 0;
+        for (uint32_t b = 1; b < bit; b <<= 1) before += (what & b) ? 1 : 0;
+        return words + ABNN_MATRIX_HEADER_WORDS + pops() + before * pops() * pops();
+    }
+    // the records from population a to population b
+    uint64_t count(uint64_t a, uint64_t b) const { return plane(ABNN_MAT_COUNT)[a * pops() + b]; }
+    // their summed weight / fire probability, in 2^-24 fixed point
+    int64_t weight(uint64_t a, uint64_t b) const { return (int64_t)plane(ABNN_MAT_W)[a * pops() + b]; }
+    int64_t fire_p(uint64_t a, uint64_t b) const { return (int64_t)plane(ABNN_MAT_P)[a * pops() + b]; }
+};
+
 // A view of a propagation result (abnn.h abnn_propagate: the header and y); it
 // does not own the words.
 struct PropagateView {
@@ -764,6 +799,24 @@ public:
                                   uint64_t* out_dev, void* stream = nullptr) const
     {
         check(abnn_components_merge_enqueue(h_, &cfg, planes_dev, n_planes, out_dev, stream), "abnn_components_merge_enqueue");
+    }
+    // Population connectivity matrix on the device (abnn_matrix; the rule is in
+    // abnn.h): the result's words, to be read through a MatrixView.  bounds_host
+    // (P + 1 values) or labels_dev (device memory, N_NRN u32), whichever the
+    // config's LABELS flag names; the other is null.
+    std::vector<uint64_t> matrix(const abnn_matrix_config& cfg, const uint32_t* bounds_host,
+                                 const uint32_t* labels_dev = nullptr) const
+    {
+        const uint64_t words = abnn_matrix_words(&cfg);
+        std::vector<uint64_t> w(words ? words : 1);
+        check(abnn_matrix(h_, &cfg, bounds_host, labels_dev, w.data(), words), "abnn_matrix");
+        return w;
+    }
+    // Enqueue only: out_dev is device memory of abnn_matrix_words(&cfg) u64.
+    void matrix_enqueue(const abnn_matrix_config& cfg, const uint32_t* bounds_host, const uint32_t* labels_dev,
+                        uint64_t* out_dev, void* stream = nullptr) const
+    {
+        check(abnn_matrix_enqueue(h_, &cfg, bounds_host, labels_dev, out_dev, stream), "abnn_matrix_enqueue");
     }
     // Reachability on the device (abnn_hops; the rule is in abnn.h): the
     // result's words, to be read through a HopsView.
